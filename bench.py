@@ -27,6 +27,9 @@ cpu_baseline = the restated reference CPU path (oracle/examg_oracle.c, generator
 
 Launch: `python bench.py` (1 GPU) or
 `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--scaling strong]`.
+A plain run sets up, settles and warms up, times the K steps and prints the headline line.  `--full` adds everything else
+(roofline, roofline_kernels, sustained_*, the V-cycle / Solve / FMG / Helmholtz / shim legs, the duplicate-plane checks at N > 1
+and cpu_baseline).  `--dump-outputs DIR` writes what the timed steps computed (dump_outputs) before anything else runs.
 """
 import argparse
 import json
@@ -69,7 +72,7 @@ def parse(argv=None):
     ap.add_argument("--extras-timeout", type=float, default=240.0, help="seconds the extra measurements may take")
     ap.add_argument("--no-check-duplicates", action="store_true",
                     help="N > 1: skip the bit-for-bit comparison of the shared duplicate planes after the timed steps and after the Solve "
-                         "(what leaving their exchange out relies on; on by default)")
+                         "(what leaving their exchange out relies on; on by default with --full)")
     ap.add_argument("--sustained-seconds", type=float, default=5.0,
                     help="after the K timed steps: the same step for at least this long, reported as sustained_* beside the headline (0: skip)")
     ap.add_argument("--blocks", default="",
@@ -77,7 +80,15 @@ def parse(argv=None):
                          "the reference's domain_rect_numBlocks of its benchmark configurations) or explicit 'bx,by,bz'")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend that carries the bootstrap / timing collectives; 'gloo': several ranks "
                                                       "on ONE GPU (the halo traffic still moves device to device through the peer-write transport)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the per-kernel and roofline figures, the sustained leg, the duplicate-plane check, the V-cycle / Solve, "
+                         "FMG, Helmholtz and shim legs and the CPU baseline (the --no-* options above switch single ones off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps: write what they computed (Solution<active>) as float64 .npy files into DIR")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def host_info():
@@ -204,6 +215,37 @@ def pmc_traffic(case, level, align):
                     rec["stale"] = True      # the kernel changed since (or the profile predates the digests): not this build's traffic
                 return rec
     return None
+
+
+DUMP_SAMPLE_POINTS = 1 << 22        # float64: 32 MiB per run, shared among the ranks
+
+
+def dump_outputs(out_dir, ops, Solution, b, e, rank, world):
+    """--dump-outputs: what the timed steps hand to a caller, Solution<active>, as float64 .npy files in `out_dir` (suffix _rank<r>
+    at N > 1).  solution_midplane.npy: the block's whole array at the middle z-plane of its updated points, [y, x];
+    solution_sample.npy: the values at a fixed sample of updated points, drawn with seed 1000 + rank (the same points in every run
+    with the same arguments), in increasing array order."""
+    import numpy as np
+    import torch
+
+    lay = Solution.layout
+    if lay.transform:
+        raise ValueError("dump_outputs: transformed layouts are not supported")
+    x = Solution.data(Solution.active)
+    tx, ty, tz = lay.tot(0), lay.tot(1), lay.tot(2)
+    updated = (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2])
+    n = min(DUMP_SAMPLE_POINTS // world, updated)
+    rng = np.random.Generator(np.random.PCG64(1000 + rank))
+    ix, iy, iz = (rng.integers(b[d], e[d], n, dtype=np.int64) + lay.ref(d) for d in range(3))
+    lin = np.sort(ix + tx * (iy + ty * iz))
+    sample = x[torch.from_numpy(lin).to(x.device)]
+    zmid = lay.ref(2) + (b[2] + e[2] - 1) // 2
+    plane = x.view(tz, ty, tx)[zmid]
+    ops.synchronize()
+    suffix = "" if world == 1 else "_rank%d" % rank
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "solution_sample%s.npy" % suffix), ops.to_host(sample).astype(np.float64, copy=False))
+    np.save(os.path.join(out_dir, "solution_midplane%s.npy" % suffix), ops.to_host(plane).astype(np.float64, copy=False))
 
 
 def main():
@@ -347,8 +389,9 @@ def run(args, world, rank, local_rank, dist, injected=False):
                 step()
             return
         if depth == 3:      # a block without neighbours: three steps per pass (examg_jacobi3), the rest as a pair or a step
-            while k >= 3 and (k - 3) != 1:
-                jacobi_triple(ops, comm, dom, Solution, RHS, A, w, Tmp)
+            # jacobi_triple does nothing and returns False where the kernel layer has no three-step pass for the box (fewer than
+            # 8e6 points): the pairs and the step below then take all k steps
+            while k >= 3 and (k - 3) != 1 and jacobi_triple(ops, comm, dom, Solution, RHS, A, w, Tmp):
                 k -= 3
         for _ in range(k // 2):
             jacobi_pair(ops, comm, dom, Solution, RHS, A, w, Tmp)
@@ -394,6 +437,46 @@ def run(args, world, rank, local_rank, dist, injected=False):
 
     if hasattr(comm, "check"):
         comm.check()           # a wait of the peer-write transport that gave up is an error, not a number
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ops, Solution, b, e, rank, world)
+    out = None
+    if rank == 0:
+        out = {
+            "metric": "LU/s",
+            "value": total_updates * args.steps / dt,
+            "unit": "LU/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "settle_steps": 2 * (args.settle_steps // 2),
+            "ms_per_step": dt / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic",
+            "config": {
+                "workload": "3D Poisson 7-point Jacobi smoother steps (ghost exchange + sweep + advance), %d x %d x %d cells per GPU, "
+                            "%s (%d-double rows)%s"
+                            % (nc[0], nc[1], nc[2],
+                               "reference field layout" if not args.align else "reference layout model with rows padded to multiples of %d doubles" % args.align,
+                               Solution.layout.tot(0),
+                               "" if depth == 1 else "; %s consecutive steps per pass over HBM (temporal blocking, bit-identical)" % ("three" if depth == 3 else "two")),
+                "blocks": list(dom.num_blocks),
+                "updates_per_step_per_gpu": updates,
+                "levels": L,
+                "align": args.align,
+            },
+        }
+        if world > 1:
+            out["transport"] = getattr(comm, "transport", None)
+            out["halo"] = "deep (two ghost layers: one exchange + one kernel per pass)" if deep else "shell (one ghost layer: interior kernel beside shell launches, two exchanges per pass)"
+            if transport_notes:
+                out["transport_notes"] = transport_notes      # transports that were tried first and did not pass the probe, and why
+    if not args.full:        # a plain run ends with the headline; everything below is --full
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return out
     if world > 1 and not args.no_check_duplicates:
         # after settle + warm-up + timed steps, all without the duplicate exchange: do both owners of every shared plane hold the same bits?
         dup_check = bool(comm.check_duplicates(Solution, Solution.active))
@@ -480,65 +563,32 @@ def run(args, world, rank, local_rank, dist, injected=False):
     if triple_ms is not None:
         extra["jacobi_three_step_kernel_ms"] = triple_ms
         extra["jacobi_three_step_frac"] = compulsory / (triple_ms * 1e-3) / 1e9 / HBM_PEAK_GBS
-    out = None
     if rank == 0:
         pmc = pmc_traffic(case, L, args.align) if nc[0] == nc[1] == nc[2] == (1 << L) else None
-        out = {
-            "metric": "LU/s",
-            "value": total_updates * args.steps / dt,
-            "unit": "LU/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "settle_steps": 2 * (args.settle_steps // 2),
-            "ms_per_step": dt / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic",
-            "config": {
-                "workload": "3D Poisson 7-point Jacobi smoother steps (ghost exchange + sweep + advance), %d x %d x %d cells per GPU, "
-                            "%s (%d-double rows)%s"
-                            % (nc[0], nc[1], nc[2],
-                               "reference field layout" if not args.align else "reference layout model with rows padded to multiples of %d doubles" % args.align,
-                               Solution.layout.tot(0),
-                               "" if depth == 1 else "; %s consecutive steps per pass over HBM (temporal blocking, bit-identical)" % ("three" if depth == 3 else "two")),
-                "blocks": list(dom.num_blocks),
-                "updates_per_step_per_gpu": updates,
-                "levels": L,
-                "align": args.align,
-            },
-            "roofline": {
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": pmc["traffic"] if (pmc and not pmc.get("stale")) else None,
-                "kernel": kernel_name,
-                "kernel_ms": kernel_ms,
-                "compulsory_bytes_per_launch": compulsory,
-                "compulsory_bytes_per_point": BYTES_PER_LU,
-                "lu_per_launch": lus,
-                # 24 B per lattice UPDATE: with two updates per pass this exceeds the peak -- a throughput
-                # statement, not a roofline fraction
-                "lu_equivalent_gbs": BYTES_PER_LU * lus / (kernel_ms * 1e-3) / 1e9,
-                "lu_equivalent_frac": BYTES_PER_LU * lus / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "traffic_over_compulsory": (pmc["traffic"] / compulsory) if (pmc and not pmc.get("stale")) else None,
-                "traffic_source": pmc["source"] if pmc else None,
-                "traffic_source_commit": pmc.get("source_commit") if pmc else None,     # the tree the counter profile was taken at
-                # True: the kernel's sources changed since that profile -- its counters are not reported as this build's traffic
-                "traffic_source_stale": bool(pmc.get("stale")) if pmc else None,
-            },
+        out["roofline"] = {
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": pmc["traffic"] if (pmc and not pmc.get("stale")) else None,
+            "kernel": kernel_name,
+            "kernel_ms": kernel_ms,
+            "compulsory_bytes_per_launch": compulsory,
+            "compulsory_bytes_per_point": BYTES_PER_LU,
+            "lu_per_launch": lus,
+            # 24 B per lattice UPDATE: with two updates per pass this exceeds the peak -- a throughput
+            # statement, not a roofline fraction
+            "lu_equivalent_gbs": BYTES_PER_LU * lus / (kernel_ms * 1e-3) / 1e9,
+            "lu_equivalent_frac": BYTES_PER_LU * lus / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "traffic_over_compulsory": (pmc["traffic"] / compulsory) if (pmc and not pmc.get("stale")) else None,
+            "traffic_source": pmc["source"] if pmc else None,
+            "traffic_source_commit": pmc.get("source_commit") if pmc else None,     # the tree the counter profile was taken at
+            # True: the kernel's sources changed since that profile -- its counters are not reported as this build's traffic
+            "traffic_source_stale": bool(pmc.get("stale")) if pmc else None,
         }
         if dup_check is not None:
             out["duplicate_planes_bit_identical"] = dup_check       # compared after the settle, warm-up and timed steps
-        if world > 1:
-            out["transport"] = getattr(comm, "transport", None)
-            out["halo"] = "deep (two ghost layers: one exchange + one kernel per pass)" if deep else "shell (one ghost layer: interior kernel beside shell launches, two exchanges per pass)"
-            if transport_notes:
-                out["transport_notes"] = transport_notes      # transports that were tried first and did not pass the probe, and why
         if sustained is not None:
             n_sus, t_sus = sustained
             out["sustained_steps"] = n_sus

@@ -25,7 +25,7 @@ def _bench(n, extra):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "10", "--warmup", "2", "--level", "7",
-           "--no-cpu-baseline", "--sustained-seconds", "0.5"] + extra
+           "--full", "--no-cpu-baseline", "--sustained-seconds", "0.5"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     return json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -86,7 +86,7 @@ def _bench_hosted(n, per, extra, level=6):
     # product's launch) stays within the default.
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", EXAMG_PEER_TIMEOUT_MS="60000", GPU_MAX_HW_QUEUES="8")
     env.pop("EXAMG_TRANSPORT", None)
-    args = ["--gpus", str(n), "--steps", "10", "--warmup", "2", "--level", str(level), "--no-cpu-baseline", "--sustained-seconds", "0.5",
+    args = ["--gpus", str(n), "--steps", "10", "--warmup", "2", "--level", str(level), "--full", "--no-cpu-baseline", "--sustained-seconds", "0.5",
             "--settle-steps", "10", "--backend", "file"] + extra
     procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "ranks_host.py"), "bench", str(q), str(n // per), str(per), boot, outp, "--"] + args,
                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env, cwd=ROOT) for q in range(n // per)]

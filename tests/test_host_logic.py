@@ -257,3 +257,52 @@ def test_block_decompositions_of_a_node():
     assert b == [0, 1, 0] and e == [16, 17, 16]           # iteration offsets 0 at interior faces, 1 / -1 at physical ones
     rb, _ = d.loop_bounds(lay, reduction=True)
     assert rb == [1, 1, 1]                                # reductions leave the lower duplicate planes to the neighbour
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample_of_updated_points(tmp_path):
+    """bench.py --dump-outputs: the middle z-plane of Solution<active> and a seeded sample of its updated points, float64, the same
+    files for the same arguments; the sample never reaches a ghost, boundary or padding point."""
+    import os
+
+    import numpy as np
+    import torch
+
+    import bench
+    from exastencils_amd.field import Field
+
+    class TorchCpuOps:
+        def new_array(self, n):
+            return torch.zeros(int(n), dtype=torch.float64)
+
+        def to_host(self, t):
+            return t.numpy()
+
+        def synchronize(self):
+            pass
+
+    ops = TorchCpuOps()
+    n = 16
+    S = Field("Solution", 4, FieldLayout.node(3, (n, n, n), 1, True, True, 4), ops, 2, None)
+    lay = S.layout
+    S.advance()
+    S.data(S.active).copy_(torch.arange(lay.size, dtype=torch.float64))     # every value is its own array index
+    b, e = [1, 1, 1], [n, n, n]
+    runs = []
+    for rep in range(2):
+        d = str(tmp_path / str(rep))
+        bench.dump_outputs(d, ops, S, b, e, 0, 1)
+        runs.append({f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    assert sorted(runs[0]) == ["solution_midplane.npy", "solution_sample.npy"]
+    for f, a in runs[0].items():
+        assert a.dtype == np.float64 and np.array_equal(a, runs[1][f])
+    idx = runs[0]["solution_sample.npy"].astype(np.int64)
+    assert len(idx) == (n - 1) ** 3 and (np.diff(idx) >= 0).all()
+    pos = (idx % lay.tot(0), idx // lay.tot(0) % lay.tot(1), idx // (lay.tot(0) * lay.tot(1)))
+    for dim in range(3):
+        assert (pos[dim] >= b[dim] + lay.ref(dim)).all() and (pos[dim] < e[dim] + lay.ref(dim)).all()
+    plane = runs[0]["solution_midplane.npy"]
+    z = lay.ref(2) + (b[2] + e[2] - 1) // 2     # the middle of the updated points 1 .. n - 1
+    assert plane.shape == (lay.tot(1), lay.tot(0)) and plane[0, 0] == z * lay.tot(0) * lay.tot(1)
+    assert bench.parse(["--dump-outputs", d]).dump_outputs == d and not bench.parse([]).full
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])

@@ -238,6 +238,60 @@ struct Geom {
 static inline Geom make_geom(const examg_geom_t *g) {
   return Geom{g->pos_begin[0], g->pos_begin[1], g->pos_begin[2], g->h[0], g->h[1], g->h[2]};
 }
+// Evaluation point of iterator index (i0, i1, i2): the node position index * h + pos_begin, or the cell centre
+// (index * h + pos_begin) + 0.5 * h (grid/ir/IR_VF_CellCenter.scala:97-100).
+template <bool CELL>
+__host__ __device__ __forceinline__ void point_position(const Geom &g, int i0, int i1, int i2, double &x, double &y, double &z) {
+  x = i0 * g.h0 + g.pb0;
+  y = i1 * g.h1 + g.pb1;
+  z = i2 * g.h2 + g.pb2;
+  if (CELL) {
+    x = x + 0.5 * g.h0;
+    y = y + 0.5 * g.h1;
+    z = z + 0.5 * g.h2;
+  }
+}
+
+// A point function: a postfix program (include/examg.h), evaluated in the order of the expression tree.
+struct ExprEval {
+  examg_expr_t e;
+  __device__ double operator()(double x, double y, double z) const {
+    double st[24];
+    int sp = 0;
+    for (int i = 0; i < e.n; ++i) {
+      switch (e.op[i]) {
+        case EXAMG_OP_CONST: st[sp++] = e.c[i]; break;
+        case EXAMG_OP_X: st[sp++] = x; break;
+        case EXAMG_OP_Y: st[sp++] = y; break;
+        case EXAMG_OP_Z: st[sp++] = z; break;
+        case EXAMG_OP_ADD: --sp; st[sp - 1] = st[sp - 1] + st[sp]; break;
+        case EXAMG_OP_SUB: --sp; st[sp - 1] = st[sp - 1] - st[sp]; break;
+        case EXAMG_OP_MUL: --sp; st[sp - 1] = st[sp - 1] * st[sp]; break;
+        case EXAMG_OP_DIV: --sp; st[sp - 1] = st[sp - 1] / st[sp]; break;
+        case EXAMG_OP_NEG: st[sp - 1] = -st[sp - 1]; break;
+        case EXAMG_OP_SIN: st[sp - 1] = sin(st[sp - 1]); break;
+        case EXAMG_OP_COS: st[sp - 1] = cos(st[sp - 1]); break;
+        case EXAMG_OP_EXP: st[sp - 1] = exp(st[sp - 1]); break;
+        case EXAMG_OP_SINH: st[sp - 1] = sinh(st[sp - 1]); break;
+        case EXAMG_OP_COSH: st[sp - 1] = cosh(st[sp - 1]); break;
+        case EXAMG_OP_SQRT: st[sp - 1] = sqrt(st[sp - 1]); break;
+        case EXAMG_OP_POW: --sp; st[sp - 1] = pow(st[sp - 1], st[sp]); break;
+        case EXAMG_OP_TAN: st[sp - 1] = tan(st[sp - 1]); break;
+        case EXAMG_OP_LOG: st[sp - 1] = log(st[sp - 1]); break;
+        case EXAMG_OP_FABS: st[sp - 1] = fabs(st[sp - 1]); break;
+        case EXAMG_OP_MAX: --sp; st[sp - 1] = fmax(st[sp - 1], st[sp]); break;
+        case EXAMG_OP_MIN: --sp; st[sp - 1] = fmin(st[sp - 1], st[sp]); break;
+        case EXAMG_OP_TANH: st[sp - 1] = tanh(st[sp - 1]); break;
+        default: st[sp++] = __builtin_nan(""); break;
+      }
+    }
+    return st[0];
+  }
+};
+
+// host check of an expression program's stack discipline (kernels_blas.hip); sets the error text when it fails
+bool expr_ok(const examg_expr_t *e);
+
 static inline Params4 make_params(const double *p) {
   Params4 q{{0, 0, 0, 0}};
   if (p) for (int i = 0; i < 4; ++i) q.v[i] = p[i];

@@ -53,6 +53,16 @@ __global__ void __launch_bounds__(256) k_set(LayoutDev l, double *x, double v, B
   }
 }
 
+__global__ void __launch_bounds__(256) k_add_scalar(LayoutDev l, double *x, double c, Box box) {
+  const long long total = box.count();
+  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+    int i0, i1, i2;
+    unflatten(box, t, i0, i1, i2);
+    const long long k = lidx(l, i0, i1, i2);
+    x[k] = x[k] + c;
+  }
+}
+
 // form: 0 => a*x   1 => x (copy)   2 => y + a*x   3 => x + b*y   4 => a*x + b*y
 // DEV: 0 none, 1 => a = sign * num/den, 2 => b = num/den (read from device memory)
 template <int DEV>
@@ -110,6 +120,8 @@ __device__ __forceinline__ double block_reduce(double v) {
   return r;  // valid in thread 0
 }
 
+// SUM: the terms are x alone (examg_sum; y is not read), else x * y
+template <bool SUM = false>
 __global__ void __launch_bounds__(RED_BLOCK)
 k_dot_partial(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const double *__restrict__ y, Box box, double *part) {
   const long long total = box.count();
@@ -117,7 +129,8 @@ k_dot_partial(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const do
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     int i0, i1, i2;
     unflatten(box, t, i0, i1, i2);
-    s = s + x[lidx(lx, i0, i1, i2)] * y[lidx(ly, i0, i1, i2)];
+    if (SUM) s = s + x[lidx(lx, i0, i1, i2)];
+    else s = s + x[lidx(lx, i0, i1, i2)] * y[lidx(ly, i0, i1, i2)];
   }
   const double r = block_reduce<false>(s);
   if (threadIdx.x == 0) part[blockIdx.x] = r;
@@ -125,6 +138,7 @@ k_dot_partial(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const do
 
 // Long rows: a wave streams whole rows, two points per lane with 16-byte loads, no index divisions per element; the rows a
 // wave takes and the order it adds them in depend only on the launch geometry, so the sum is reproducible run to run.
+template <bool SUM = false>
 __global__ void __launch_bounds__(RED_BLOCK)
 k_dot_rows(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const double *__restrict__ y, Box box, double *part) {
   const int lane = threadIdx.x & 63;
@@ -135,9 +149,17 @@ k_dot_rows(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const doubl
   double s = 0.0;
   for (long long r = wave; r < nrows; r += nwaves) {
     const int i1 = box.b1 + (int)(r % n1), i2 = box.b2 + (int)(r / n1);
-    const double *px = x + lidx(lx, 0, i1, i2), *py = y + lidx(ly, 0, i1, i2);
+    const double *px = x + lidx(lx, 0, i1, i2), *py = SUM ? px : y + lidx(ly, 0, i1, i2);
     for (int i0 = box.b0 + 2 * lane; i0 < box.e0; i0 += 128) {
-      if (i0 + 1 < box.e0) {
+      if (SUM) {
+        if (i0 + 1 < box.e0) {
+          const d2 a = load2(px + i0);
+          s = s + a.x;
+          s = s + a.y;
+        } else {
+          s = s + px[i0];
+        }
+      } else if (i0 + 1 < box.e0) {
         const d2 a = load2(px + i0), b = load2(py + i0);
         s = s + a.x * b.x;
         s = s + a.y * b.y;
@@ -150,44 +172,8 @@ k_dot_rows(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const doubl
   if (threadIdx.x == 0) part[blockIdx.x] = r;
 }
 
-// A point function: a postfix program (include/examg.h), evaluated in the order of the expression tree.
-struct ExprEval {
-  examg_expr_t e;
-  __device__ double operator()(double x, double y, double z) const {
-    double st[24];
-    int sp = 0;
-    for (int i = 0; i < e.n; ++i) {
-      switch (e.op[i]) {
-        case EXAMG_OP_CONST: st[sp++] = e.c[i]; break;
-        case EXAMG_OP_X: st[sp++] = x; break;
-        case EXAMG_OP_Y: st[sp++] = y; break;
-        case EXAMG_OP_Z: st[sp++] = z; break;
-        case EXAMG_OP_ADD: --sp; st[sp - 1] = st[sp - 1] + st[sp]; break;
-        case EXAMG_OP_SUB: --sp; st[sp - 1] = st[sp - 1] - st[sp]; break;
-        case EXAMG_OP_MUL: --sp; st[sp - 1] = st[sp - 1] * st[sp]; break;
-        case EXAMG_OP_DIV: --sp; st[sp - 1] = st[sp - 1] / st[sp]; break;
-        case EXAMG_OP_NEG: st[sp - 1] = -st[sp - 1]; break;
-        case EXAMG_OP_SIN: st[sp - 1] = sin(st[sp - 1]); break;
-        case EXAMG_OP_COS: st[sp - 1] = cos(st[sp - 1]); break;
-        case EXAMG_OP_EXP: st[sp - 1] = exp(st[sp - 1]); break;
-        case EXAMG_OP_SINH: st[sp - 1] = sinh(st[sp - 1]); break;
-        case EXAMG_OP_COSH: st[sp - 1] = cosh(st[sp - 1]); break;
-        case EXAMG_OP_SQRT: st[sp - 1] = sqrt(st[sp - 1]); break;
-        case EXAMG_OP_POW: --sp; st[sp - 1] = pow(st[sp - 1], st[sp]); break;
-        case EXAMG_OP_TAN: st[sp - 1] = tan(st[sp - 1]); break;
-        case EXAMG_OP_LOG: st[sp - 1] = log(st[sp - 1]); break;
-        case EXAMG_OP_FABS: st[sp - 1] = fabs(st[sp - 1]); break;
-        case EXAMG_OP_MAX: --sp; st[sp - 1] = fmax(st[sp - 1], st[sp]); break;
-        case EXAMG_OP_MIN: --sp; st[sp - 1] = fmin(st[sp - 1], st[sp]); break;
-        case EXAMG_OP_TANH: st[sp - 1] = tanh(st[sp - 1]); break;
-        default: st[sp++] = __builtin_nan(""); break;
-      }
-    }
-    return st[0];
-  }
-};
 
-template <class F>
+template <class F, bool CELL = false>
 __global__ void __launch_bounds__(RED_BLOCK)
 k_maxerr_partial(LayoutDev l, const double *__restrict__ x, Geom g, F fn, Box box, double *part) {
   const long long total = box.count();
@@ -195,7 +181,8 @@ k_maxerr_partial(LayoutDev l, const double *__restrict__ x, Geom g, F fn, Box bo
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     int i0, i1, i2;
     unflatten(box, t, i0, i1, i2);
-    const double px = i0 * g.h0 + g.pb0, py = i1 * g.h1 + g.pb1, pz = i2 * g.h2 + g.pb2;
+    double px, py, pz;
+    point_position<CELL>(g, i0, i1, i2, px, py, pz);
     m = fmax(m, fabs(x[lidx(l, i0, i1, i2)] - fn(px, py, pz)));
   }
   const double r = block_reduce<true>(m);
@@ -211,13 +198,14 @@ __global__ void __launch_bounds__(RED_BLOCK) k_reduce_final(const double *part, 
 }
 
 // ---- analytic fills ---------------------------------------------------------------------------
-template <class F>
+template <class F, bool CELL = false>
 __global__ void __launch_bounds__(256) k_fill_fn(LayoutDev l, double *x, Geom g, F fn, Box box) {
   const long long total = box.count();
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     int i0, i1, i2;
     unflatten(box, t, i0, i1, i2);
-    const double px = i0 * g.h0 + g.pb0, py = i1 * g.h1 + g.pb1, pz = i2 * g.h2 + g.pb2;
+    double px, py, pz;
+    point_position<CELL>(g, i0, i1, i2, px, py, pz);
     x[lidx(l, i0, i1, i2)] = fn(px, py, pz);
   }
 }
@@ -401,15 +389,45 @@ extern "C" int examg_dot(const examg_layout_t *lx_, const double *x, const examg
   if (!box_inside(lx_, box, 0) || !box_inside(ly_, box, 0)) { set_error("examg_dot: box leaves an allocation"); return 1; }
   const int nb = red_blocks(box.count());
   if (box.n0() >= 128 && !lay_split(lx_) && !lay_split(ly_))
-    hipLaunchKernelGGL(k_dot_rows, dim3(nb), dim3(RED_BLOCK), 0, s, make_layout(lx_), x, make_layout(ly_), y, box, (double *)work);
+    hipLaunchKernelGGL(k_dot_rows<false>, dim3(nb), dim3(RED_BLOCK), 0, s, make_layout(lx_), x, make_layout(ly_), y, box, (double *)work);
   else
-    hipLaunchKernelGGL(k_dot_partial, dim3(nb), dim3(RED_BLOCK), 0, s, make_layout(lx_), x, make_layout(ly_), y, box, (double *)work);
+    hipLaunchKernelGGL(k_dot_partial<false>, dim3(nb), dim3(RED_BLOCK), 0, s, make_layout(lx_), x, make_layout(ly_), y, box, (double *)work);
   hipLaunchKernelGGL((k_reduce_final<false>), dim3(1), dim3(RED_BLOCK), 0, s, (const double *)work, nb, result);
   EXAMG_CHECK_LAUNCH("k_dot");
   return 0;
 }
 
-template <class F>
+// examg_dot's kernels and reduction tree with the terms x alone
+extern "C" int examg_sum(const examg_layout_t *l_, const double *x, const int32_t *begin, const int32_t *end, double *result, void *work,
+                         examg_stream_t stream) {
+  if (!l_ || !x || !begin || !end || !result || !work) { set_error("examg_sum: null argument"); return 1; }
+  const Box box = make_box(begin, end);
+  hipStream_t s = (hipStream_t)stream;
+  if (box.count() == 0) return check_hip(hipMemsetAsync(result, 0, sizeof(double), s), "examg_sum memset");
+  if (!box_inside(l_, box, 0)) { set_error("examg_sum: box leaves the allocation"); return 1; }
+  const int nb = red_blocks(box.count());
+  const LayoutDev l = make_layout(l_);
+  if (box.n0() >= 128 && !lay_split(l_))
+    hipLaunchKernelGGL(k_dot_rows<true>, dim3(nb), dim3(RED_BLOCK), 0, s, l, x, l, x, box, (double *)work);
+  else
+    hipLaunchKernelGGL(k_dot_partial<true>, dim3(nb), dim3(RED_BLOCK), 0, s, l, x, l, x, box, (double *)work);
+  hipLaunchKernelGGL((k_reduce_final<false>), dim3(1), dim3(RED_BLOCK), 0, s, (const double *)work, nb, result);
+  EXAMG_CHECK_LAUNCH("k_sum");
+  return 0;
+}
+
+extern "C" int examg_add_scalar(const examg_layout_t *l_, double *x, double c, const int32_t *begin, const int32_t *end,
+                                examg_stream_t stream) {
+  if (!l_ || !x || !begin || !end) { set_error("examg_add_scalar: null argument"); return 1; }
+  const Box box = make_box(begin, end);
+  if (box.count() == 0) return 0;
+  if (!box_inside(l_, box, 0)) { set_error("examg_add_scalar: box leaves the allocation"); return 1; }
+  hipLaunchKernelGGL(k_add_scalar, grid_for(box.count()), dim3(256), 0, (hipStream_t)stream, make_layout(l_), x, c, box);
+  EXAMG_CHECK_LAUNCH("k_add_scalar");
+  return 0;
+}
+
+template <class F, bool CELL = false>
 static int max_err_impl(const char *who, const examg_layout_t *l_, const double *x, const examg_geom_t *g, const F &fn,
                         const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream) {
   if (!l_ || !x || !g || !begin || !end || !result || !work) { set_error("examg_max_err: null argument"); return 1; }
@@ -418,20 +436,20 @@ static int max_err_impl(const char *who, const examg_layout_t *l_, const double 
   if (box.count() == 0) return check_hip(hipMemsetAsync(result, 0, sizeof(double), s), "examg_max_err memset");
   if (!box_inside(l_, box, 0)) { set_error("examg_max_err: box leaves the allocation"); return 1; }
   const int nb = red_blocks(box.count());
-  hipLaunchKernelGGL((k_maxerr_partial<F>), dim3(nb), dim3(RED_BLOCK), 0, s, make_layout(l_), x, make_geom(g), fn, box, (double *)work);
+  hipLaunchKernelGGL((k_maxerr_partial<F, CELL>), dim3(nb), dim3(RED_BLOCK), 0, s, make_layout(l_), x, make_geom(g), fn, box, (double *)work);
   hipLaunchKernelGGL((k_reduce_final<true>), dim3(1), dim3(RED_BLOCK), 0, s, (const double *)work, nb, result);
   EXAMG_CHECK_LAUNCH(who);
   return 0;
 }
 
-template <class F>
+template <class F, bool CELL = false>
 static int fill_impl(const char *who, const examg_layout_t *l_, double *x, const examg_geom_t *g, const F &fn, const int32_t *begin,
                      const int32_t *end, examg_stream_t stream) {
   if (!l_ || !x || !g || !begin || !end) { set_error("examg_fill: null argument"); return 1; }
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   if (!box_inside(l_, box, 0)) { set_error("examg_fill: box leaves the allocation"); return 1; }
-  hipLaunchKernelGGL((k_fill_fn<F>), grid_for(box.count()), dim3(256), 0, (hipStream_t)stream, make_layout(l_), x, make_geom(g), fn, box);
+  hipLaunchKernelGGL((k_fill_fn<F, CELL>), grid_for(box.count()), dim3(256), 0, (hipStream_t)stream, make_layout(l_), x, make_geom(g), fn, box);
   EXAMG_CHECK_LAUNCH(who);
   return 0;
 }
@@ -468,7 +486,7 @@ static int dirichlet_impl(const char *who, const examg_layout_t *l, double *x, c
   return 0;
 }
 
-static bool expr_ok(const examg_expr_t *e) {
+bool examg::expr_ok(const examg_expr_t *e) {
   if (!e || e->n < 1 || e->n > EXAMG_MAX_EXPR) { set_error("examg expression: null or too long"); return false; }
   int sp = 0;      // the stack discipline is checked on the host, the kernel trusts it
   for (int i = 0; i < e->n; ++i) {
@@ -500,6 +518,18 @@ extern "C" int examg_fill_expr(const examg_layout_t *l_, double *x, const examg_
                                const int32_t *begin, const int32_t *end, examg_stream_t stream) {
   if (!expr_ok(e)) return 1;
   return fill_impl("k_fill_expr", l_, x, g, ExprEval{*e}, begin, end, stream);
+}
+
+extern "C" int examg_max_err_expr_cell(const examg_layout_t *l_, const double *x, const examg_geom_t *g, const examg_expr_t *e,
+                                       const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream) {
+  if (!expr_ok(e)) return 1;
+  return max_err_impl<ExprEval, true>("k_maxerr_expr_cell", l_, x, g, ExprEval{*e}, begin, end, result, work, stream);
+}
+
+extern "C" int examg_fill_expr_cell(const examg_layout_t *l_, double *x, const examg_geom_t *g, const examg_expr_t *e,
+                                    const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  if (!expr_ok(e)) return 1;
+  return fill_impl<ExprEval, true>("k_fill_expr_cell", l_, x, g, ExprEval{*e}, begin, end, stream);
 }
 
 extern "C" int examg_apply_dirichlet_expr(const examg_layout_t *l, double *x, const examg_geom_t *g, const examg_expr_t *e,

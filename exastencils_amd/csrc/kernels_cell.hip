@@ -1,0 +1,304 @@
+// Cell-centred fields on gfx950: ghost-layer boundary conditions and the linear cell transfer operators.
+//
+// Reference: `Layout X< Real, Cell >` fields (Testing/CellBased/{2D,3D}_{Basic,Neumann}.exa4); boundary updates
+// Compiler/src/exastencils/boundary/ir/IR_DirichletBC.scala / IR_NeumannBC.scala (generateFieldUpdatesCell, order 1) over the
+// boundary row of boundary/ir/IR_ApplyBCFunction.scala:53-83, face-centre coordinates boundary/ir/IR_HandleBoundaries.scala:55-70;
+// transfer stencils operator/l4/L4_DefaultRestriction.scala:37-43,63-90 and L4_DefaultProlongation.scala:30-45.
+//
+// The transfer kernels are pure streams (8 B in, 1 B out per fine cell for the restriction; 8 B in, 8 B out, 1 B in for the
+// prolongation): a wave owns a contiguous x-run of 64 coarse cells of one coarse row; lane l takes coarse cell I = first + l,
+// whose two fine x-children (2I, 2I+1) are adjacent -- one 16-byte load (or store) per fine row where the fine rows start
+// 16-byte aligned (FieldLayout.cell(..., align=2)), two 8-byte accesses otherwise; both forms compute the same bits.  A wave
+// covers all 2^(d-1) fine rows of its coarse row, so every fine value is read once and every coarse value once per wave.
+#include "examg_common.h"
+
+namespace examg {
+
+// ---- apply bc ---------------------------------------------------------------------------------------------------------------
+struct CellFaces {
+  Box box[6];          // the boundary row of cells of each face (iterator coordinates)
+  int dim[6], up[6];   // normal dimension, 1 for the upper side
+  long long start[7];  // prefix sums of the counts
+  int n;
+};
+
+// One launch for every face of the mask.  Thread t -> (face, boundary cell); the ghost is the cell one step outwards.
+template <int KIND>
+__global__ void __launch_bounds__(256) k_apply_bc_cell(LayoutDev l, double *x, Geom g, ExprEval fn, CellFaces fc, int3 inner) {
+  const long long total = fc.start[fc.n];
+  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+    int f = 0;
+    while (f + 1 < fc.n && t >= fc.start[f + 1]) ++f;
+    const Box &bx = fc.box[f];
+    const long long r = t - fc.start[f];
+    const int n0 = bx.n0(), n1 = bx.n1();
+    int i[3];
+    i[0] = bx.b0 + (int)(r % n0);
+    i[1] = bx.b1 + (int)((r / n0) % n1);
+    i[2] = bx.b2 + (int)(r / ((long long)n0 * n1));
+    const int d = fc.dim[f], up = fc.up[f];
+    int o[3] = {i[0], i[1], i[2]};
+    o[d] += up ? 1 : -1;
+    const double interior = x[lidx(l, i[0], i[1], i[2])];
+    double v;
+    if (KIND == EXAMG_BC_NEUMANN) {
+      v = interior;
+    } else {
+      // face centre: cell centres tangentially, the node position of the face (index 0 / inner) in the normal dimension
+      double p[3];
+      point_position<true>(g, i[0], i[1], i[2], p[0], p[1], p[2]);
+      const double hh[3] = {g.h0, g.h1, g.h2}, pb[3] = {g.pb0, g.pb1, g.pb2};
+      const int nidx = up ? (d == 0 ? inner.x : (d == 1 ? inner.y : inner.z)) : 0;
+      p[d] = nidx * hh[d] + pb[d];
+      v = (2.0 * fn(p[0], p[1], p[2])) - interior;
+    }
+    x[lidx(l, o[0], o[1], o[2])] = v;
+  }
+}
+
+// ---- restriction ----------------------------------------------------------------------------------------------------------
+// XCD bands: workgroups are dealt round-robin to the 8 XCDs; within a z layer every XCD takes a band of consecutive workgroups
+// (x tiles fastest, then coarse rows), so the cache lines that x-adjacent tiles share meet in one L2 (kernels_transfer.hip:
+// k_restrict3_wide).
+__device__ __forceinline__ long long xcd_band(long long wg, int wpl) {
+  if ((wpl & 7) == 0) {
+    const int per = wpl >> 3;
+    const long long lz = wg / wpl;
+    const int r = (int)(wg - lz * wpl);
+    return lz * wpl + (r & 7) * per + (r >> 3);
+  }
+  return wg;
+}
+
+// fc(I) = sum_{a, b, c in {0,1}} (scale * 0.5^d) * rf(2I + (a, b, c)), terms added in the entry order of the composed stencil
+// kron(kron(Rx, Ry), Rz) (L4_StencilOps.kron: left entries outer, right entries inner): x offset outermost, then y, then z.
+// VEC: the pair (2I, 2I+1) of every fine row with one aligned 16-byte load.
+template <int ND, bool VEC>
+__global__ void __launch_bounds__(256)
+k_restrict_cell(LayoutDev lf, const double *__restrict__ rf, LayoutDev lc, double *__restrict__ fc, double wgt, Box box, int ntx, int nwaves) {
+  const int lane = threadIdx.x;
+  const long long wg = xcd_band(blockIdx.x, ntx * ((box.n1() + 3) >> 2));
+  const int wpl = ntx * ((box.n1() + 3) >> 2);
+  const long long lz = wg / wpl;
+  const int r = (int)(wg - lz * wpl);
+  const int tx = r % ntx;
+  const int jw = (r / ntx) * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.y);
+  if (jw >= box.n1()) return;
+  const long long w = lz * box.n1() + jw;
+  if (w >= nwaves) return;
+  const int I0 = box.b0 + tx * 64 + lane;
+  if (I0 >= box.e0) return;
+  const int I1 = box.b1 + jw;
+  const int I2 = box.b2 + (int)lz;
+  constexpr int NR = ND == 3 ? 4 : 2;     // fine rows of the coarse cell: (b, c) with b outer
+  double v[NR][2];
+#pragma unroll
+  for (int q = 0; q < NR; ++q) {
+    const int b = ND == 3 ? (q >> 1) : q, c = ND == 3 ? (q & 1) : 0;
+    const double *p = rf + lidx_plain(lf, 2 * I0, 2 * I1 + b, ND == 3 ? 2 * I2 + c : 0);
+    if (VEC) {
+      const d2 t = *reinterpret_cast<const d2 *>(p);
+      v[q][0] = t.x;
+      v[q][1] = t.y;
+    } else {
+      v[q][0] = p[0];
+      v[q][1] = p[1];
+    }
+  }
+  double acc = wgt * v[0][0];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int q = 0; q < NR; ++q) {
+      if (a == 0 && q == 0) continue;
+      acc = acc + wgt * v[q][a];
+    }
+  fc[lidx_plain(lc, I0, I1, I2)] = acc;
+}
+
+// ---- prolongation + correction --------------------------------------------------------------------------------------------
+// uf(i) = uf(i) + uc(floor(i / 2)) over the fine box.  Lane l takes the fine pair (2I, 2I+1) of coarse cell I = I0first + l in
+// every fine row of coarse row (J, K) that lies in the box: one coarse load serves 2^d fine cells.
+template <int ND, bool VEC>
+__global__ void __launch_bounds__(256)
+k_prolong_add_cell(LayoutDev lc, const double *__restrict__ uc, LayoutDev lf, double *__restrict__ uf, Box box, int cb0, int cb1, int cb2,
+                   int nc0, int nc1, int ntx, int nwaves) {
+  const int lane = threadIdx.x;
+  const int wpl = ntx * ((nc1 + 3) >> 2);
+  const long long wg = xcd_band(blockIdx.x, wpl);
+  const long long lz = wg / wpl;
+  const int r = (int)(wg - lz * wpl);
+  const int tx = r % ntx;
+  const int jw = (r / ntx) * 4 + (int)__builtin_amdgcn_readfirstlane(threadIdx.y);
+  if (jw >= nc1) return;
+  const long long w = lz * nc1 + jw;
+  if (w >= nwaves) return;
+  const int ci = tx * 64 + lane;
+  if (ci >= nc0) return;
+  const int I0 = cb0 + ci, I1 = cb1 + jw, I2 = cb2 + (int)lz;
+  const double c = uc[lidx_plain(lc, I0, I1, I2)];
+  const int f0 = 2 * I0;
+  const bool ok0 = f0 >= box.b0, ok1 = f0 + 1 < box.e0;
+#pragma unroll
+  for (int q = 0; q < (ND == 3 ? 4 : 2); ++q) {
+    const int j = 2 * I1 + (ND == 3 ? (q >> 1) : q), k = ND == 3 ? 2 * I2 + (q & 1) : box.b2;
+    if (j < box.b1 || j >= box.e1 || k < box.b2 || k >= box.e2) continue;
+    double *p = uf + lidx_plain(lf, f0, j, k);
+    if (VEC && ok0 && ok1) {
+      d2 t = *reinterpret_cast<d2 *>(p);
+      t.x = t.x + c;
+      t.y = t.y + c;
+      *reinterpret_cast<d2 *>(p) = t;
+    } else {
+      if (ok0) p[0] = p[0] + c;
+      if (ok1) p[1] = p[1] + c;
+    }
+  }
+}
+
+static bool cell_layout_ok(const char *who, const examg_layout_t *l) {
+  for (int d = 0; d < l->nd; ++d)
+    if (l->dup_l[d] != 0 || l->dup_r[d] != 0) {
+      set_error("%s: a cell layout has no duplicate layers (dim %d has %d / %d)", who, d, l->dup_l[d], l->dup_r[d]);
+      return false;
+    }
+  if (lay_split(l)) { set_error("%s: cell layouts under a layout transformation are not supported", who); return false; }
+  return true;
+}
+
+// 16-byte access to the fine pair (2I, 2I+1) of every fine row: the pointer and the linear index of every even fine x index
+// are even (reference offset and row strides even)
+static bool pairs_aligned(const examg_layout_t *l, const double *p) {
+  const LayoutDev d = make_layout(l);
+  return ((uintptr_t)p & 15) == 0 && (d.origin & 1) == 0 && (d.s1 & 1) == 0 && (l->nd < 3 || (d.s2 & 1) == 0);
+}
+
+static int g_force_narrow = 0;   // debug build: force the 8-byte form
+
+}  // namespace examg
+
+using namespace examg;
+
+#ifdef EXAMG_DEBUG_HOOKS
+extern "C" int examg_debug_cell_narrow(int on) {
+  g_force_narrow = on;
+  return 0;
+}
+#endif
+
+extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
+                                   uint32_t face_mask, examg_stream_t stream) {
+  if (!l || !x || !g) { set_error("examg_apply_bc_cell: null argument"); return 1; }
+  if (kind != EXAMG_BC_DIRICHLET && kind != EXAMG_BC_NEUMANN) { set_error("examg_apply_bc_cell: unknown kind %d", kind); return 1; }
+  if (kind == EXAMG_BC_DIRICHLET && !expr_ok(expr)) return 1;
+  if (!cell_layout_ok("examg_apply_bc_cell", l)) return 1;
+  CellFaces fc;
+  fc.n = 0;
+  fc.start[0] = 0;
+  for (int d = 0; d < l->nd; ++d)
+    for (int side = 0; side < 2; ++side) {
+      if (!(face_mask & (1u << (2 * d + side)))) continue;
+      if ((side ? l->ghost_r[d] : l->ghost_l[d]) < 1) {
+        set_error("examg_apply_bc_cell: face %d of dim %d has no ghost layer", side, d);
+        return 1;
+      }
+      int b[3] = {0, 0, 0}, e[3] = {1, 1, 1};
+      for (int t = 0; t < l->nd; ++t) {
+        b[t] = 0;
+        e[t] = l->inner[t];
+      }
+      if (side == 0) e[d] = 1;
+      else b[d] = l->inner[d] - 1;
+      const Box bx{b[0], b[1], b[2], e[0], e[1], e[2]};
+      if (bx.count() == 0) continue;
+      fc.box[fc.n] = bx;
+      fc.dim[fc.n] = d;
+      fc.up[fc.n] = side;
+      fc.start[fc.n + 1] = fc.start[fc.n] + bx.count();
+      ++fc.n;
+    }
+  if (fc.n == 0) return 0;
+  examg_expr_t none;
+  if (kind == EXAMG_BC_NEUMANN) {
+    none.n = 1;
+    none.op[0] = EXAMG_OP_CONST;
+    none.c[0] = 0.0;
+  }
+  const ExprEval fn{kind == EXAMG_BC_NEUMANN ? none : *expr};
+  const int3 inner = make_int3(l->inner[0], l->inner[1], l->inner[2]);
+  const long long total = fc.start[fc.n];
+  long long nb = (total + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  hipStream_t s = (hipStream_t)stream;
+  if (kind == EXAMG_BC_NEUMANN)
+    hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_NEUMANN>), dim3((unsigned)nb), dim3(256), 0, s, make_layout(l), x, make_geom(g), fn, fc, inner);
+  else
+    hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_DIRICHLET>), dim3((unsigned)nb), dim3(256), 0, s, make_layout(l), x, make_geom(g), fn, fc, inner);
+  EXAMG_CHECK_LAUNCH("k_apply_bc_cell");
+  return 0;
+}
+
+extern "C" int examg_restrict_cell(const examg_layout_t *lf_, const double *rf, const examg_layout_t *lc_, double *fc, double scale,
+                                   const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  if (!lf_ || !rf || !lc_ || !fc || !begin || !end) { set_error("examg_restrict_cell: null argument"); return 1; }
+  if (!cell_layout_ok("examg_restrict_cell", lf_) || !cell_layout_ok("examg_restrict_cell", lc_)) return 1;
+  if (lf_->nd != lc_->nd || lf_->nd < 2) { set_error("examg_restrict_cell: 2-D or 3-D layouts of one dimensionality"); return 1; }
+  const Box box = make_box(begin, end);
+  if (box.count() == 0) return 0;
+  const int nd = lf_->nd;
+  const Box fine{2 * box.b0, 2 * box.b1, nd == 3 ? 2 * box.b2 : 0, 2 * box.e0, 2 * box.e1, nd == 3 ? 2 * box.e2 : 1};
+  if (!box_inside(lc_, box, 0) || !box_inside(lf_, fine, 0)) { set_error("examg_restrict_cell: box leaves an allocation"); return 1; }
+  if (nd == 2 && (box.b2 != 0 || box.e2 != 1)) { set_error("examg_restrict_cell: 2-D box must have [0,1) in dim 2"); return 1; }
+  const double wgt = scale * (nd == 3 ? 0.125 : 0.25);
+  const int ntx = (box.n0() + 63) / 64;
+  const long long nwaves = (long long)box.n1() * box.n2();
+  const long long nwg = (long long)ntx * ((box.n1() + 3) / 4) * box.n2();
+  if (nwg > 0x7fffffffLL) { set_error("examg_restrict_cell: grid too large"); return 1; }
+  const bool vec = !g_force_narrow && pairs_aligned(lf_, rf);
+  const LayoutDev lf = make_layout(lf_), lc = make_layout(lc_);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)nwg), blk(64, 4);
+  if (nd == 3) {
+    if (vec) hipLaunchKernelGGL((k_restrict_cell<3, true>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves);
+    else hipLaunchKernelGGL((k_restrict_cell<3, false>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves);
+  } else {
+    if (vec) hipLaunchKernelGGL((k_restrict_cell<2, true>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves);
+    else hipLaunchKernelGGL((k_restrict_cell<2, false>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves);
+  }
+  EXAMG_CHECK_LAUNCH("k_restrict_cell");
+  return 0;
+}
+
+extern "C" int examg_prolong_add_cell(const examg_layout_t *lc_, const double *uc, const examg_layout_t *lf_, double *uf,
+                                      const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  if (!lc_ || !uc || !lf_ || !uf || !begin || !end) { set_error("examg_prolong_add_cell: null argument"); return 1; }
+  if (!cell_layout_ok("examg_prolong_add_cell", lf_) || !cell_layout_ok("examg_prolong_add_cell", lc_)) return 1;
+  if (lf_->nd != lc_->nd || lf_->nd < 2) { set_error("examg_prolong_add_cell: 2-D or 3-D layouts of one dimensionality"); return 1; }
+  const Box box = make_box(begin, end);
+  if (box.count() == 0) return 0;
+  const int nd = lf_->nd;
+  if (nd == 2 && (box.b2 != 0 || box.e2 != 1)) { set_error("examg_prolong_add_cell: 2-D box must have [0,1) in dim 2"); return 1; }
+  // parent box: floor(i / 2) over the fine box (arithmetic shifts floor negative indices too)
+  const int cb0 = box.b0 >> 1, cb1 = box.b1 >> 1, cb2 = nd == 3 ? box.b2 >> 1 : 0;
+  const int ce0 = ((box.e0 - 1) >> 1) + 1, ce1 = ((box.e1 - 1) >> 1) + 1, ce2 = nd == 3 ? ((box.e2 - 1) >> 1) + 1 : 1;
+  const Box cbox{cb0, cb1, cb2, ce0, ce1, ce2};
+  if (!box_inside(lf_, box, 0) || !box_inside(lc_, cbox, 0)) { set_error("examg_prolong_add_cell: box leaves an allocation"); return 1; }
+  const int nc0 = ce0 - cb0, nc1 = ce1 - cb1, nc2 = ce2 - cb2;
+  const int ntx = (nc0 + 63) / 64;
+  const long long nwaves = (long long)nc1 * nc2;
+  const long long nwg = (long long)ntx * ((nc1 + 3) / 4) * nc2;
+  if (nwg > 0x7fffffffLL) { set_error("examg_prolong_add_cell: grid too large"); return 1; }
+  const bool vec = !g_force_narrow && pairs_aligned(lf_, uf);
+  const LayoutDev lc = make_layout(lc_), lf = make_layout(lf_);
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)nwg), blk(64, 4);
+  if (nd == 3) {
+    if (vec) hipLaunchKernelGGL((k_prolong_add_cell<3, true>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves);
+    else hipLaunchKernelGGL((k_prolong_add_cell<3, false>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves);
+  } else {
+    if (vec) hipLaunchKernelGGL((k_prolong_add_cell<2, true>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves);
+    else hipLaunchKernelGGL((k_prolong_add_cell<2, false>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves);
+  }
+  EXAMG_CHECK_LAUNCH("k_prolong_add_cell");
+  return 0;
+}

@@ -126,8 +126,13 @@ class RectDomain:
     def loop_bounds(self, layout, reduction: bool = False):
         """Iteration space of `loop over <field>` (baseExt/ir/IR_LoopOverPointsInOneFragment.scala:84-101):
         [DLB + iterationOffsetBegin, DRE + iterationOffsetEnd), offsets 1 / -1 on a physical boundary and 0
-        at an interior block face; reduction loops skip the lower duplicate plane (:116-125)."""
+        at an interior block face; reduction loops skip the lower duplicate plane (:116-125).  A cell layout (the IR_AtCellCenter
+        case) has no duplicate plane: [DLB, DRE) = every inner cell, whatever the neighbours, for reductions too."""
         b, e = [0, 0, 0], [1, 1, 1]
+        if getattr(layout, "localization", "node") == "cell":
+            for d in range(self.nd):
+                b[d], e[d] = layout.idx("DLB", d), layout.idx("DRE", d)
+            return b, e
         for d in range(self.nd):
             b[d] = layout.idx("DLB", d) + (0 if self.neighbor(d, -1) is not None else 1)
             e[d] = layout.idx("DRE", d) + (0 if self.neighbor(d, +1) is not None else -1)

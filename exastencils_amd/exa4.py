@@ -139,6 +139,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
         self._bc_epoch: Dict[Tuple[str, int], int] = {}
         self._pair_tmp: Dict[Tuple[str, int], Field] = {}
         self._bc_valid = set()      # (field, level, slot) whose physical-boundary planes hold the field's Dirichlet values
+        self._cell_names = set()    # fields declared on a cell layout: never taken by a one-pass peephole or cross-statement fusion
         self._lazy_init()           # pending loops of the cross-statement fusions (exastencils_amd/exa4_fusion.py)
         self._declare()
 
@@ -186,10 +187,15 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
             ld = layouts.get(fd.layout)
             if ld is None:
                 raise Exa4SyntaxError("field %s uses the undeclared layout %s" % (fd.name, fd.layout))
-            if ld.localization != "Node":
-                raise Exa4Unsupported("layout %s: localization %s (node fields only)" % (ld.name, ld.localization))
+            if ld.localization not in ("Node", "Cell"):
+                raise Exa4Unsupported("layout %s: localization %s (node and cell fields only)" % (ld.name, ld.localization))
             if ld.vec_len != 1 and fd.name not in sfield_fields:
                 raise Exa4Unsupported("vector-valued field %s outside a StencilField" % fd.name)
+            if ld.localization == "Cell":
+                self._declare_cell_field(fd, ld, nslots[fd.name], sfield_fields)
+                continue
+            if self._bc_kind(fd.bc) is not None:
+                raise Exa4Unsupported("field %s: Neumann boundary conditions on node fields" % fd.name)
             for lvl in self.levels_of(fd.levels):
                 if (fd.name, lvl) in self.fields or not (self.min_level <= lvl <= self.max_level):
                     continue
@@ -235,6 +241,100 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                     raise Exa4SyntaxError("stencil field %s: %d entries but %d coefficients per point" % (sf.name, len(offs), getattr(cf, "vec_len", 1)))
                 self.stencils[(sf.name, lvl)] = Stencil(offs, [], cf.slots[0], cf.layout)
         self._apply_layout_transformations()
+
+    # -- cell-centred fields ------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _bc_kind(bc):
+        """The order of a `Neumann` / `Neumann(n)` boundary condition, None for Dirichlet values (or no condition)."""
+        if bc is None:
+            return None
+        if bc[0] == "id" and bc[1] == "Neumann":
+            return 1
+        if bc[0] == "call" and bc[1] == "Neumann":
+            return int(_const_value(bc[3][0])) if len(bc[3]) == 1 else -1
+        return None
+
+    def _declare_cell_field(self, fd, ld, nslots: int, sfield_fields):
+        """`Layout X< Real, Cell >`: no duplicate layers, one value per cell (fragLen * 2^level per dimension), boundary
+        conditions in the ghost layer (examg_apply_bc_cell)."""
+        from .lib import BC_DIRICHLET, BC_NEUMANN
+
+        nd, dom = self.nd, self.domain
+        if ld.vec_len != 1 or fd.name in sfield_fields:
+            raise Exa4Unsupported("layout %s: vector-valued cell fields" % ld.name)
+        if any(dom.periodic[:nd]):
+            raise Exa4Unsupported("field %s: cell fields on a periodic domain" % fd.name)
+        if any((ld.dup[i] if i < len(ld.dup) else 0) != 0 for i in range(nd)):
+            raise Exa4Unsupported("layout %s: a cell layout has no duplicate layers" % ld.name)
+        if ld.inner:
+            raise Exa4Unsupported("layout %s: innerPoints on a cell layout" % ld.name)
+        for key in ("discr_defaultDirichletOrder", "discr_defaultNeumannOrder"):
+            if int(self.k.get(key, 1)) != 1:
+                raise Exa4Unsupported("%s = %s: boundary conditions of order 2 on cell fields" % (key, self.k[key]))
+        order = self._bc_kind(fd.bc)
+        if order is not None and order != 1:
+            raise Exa4Unsupported("field %s: Neumann(%d) -- boundary conditions of order 2 on cell fields" % (fd.name, order))
+        self._cell_names.add(fd.name)
+        ghost = tuple(ld.ghost[i] if i < nd and i < len(ld.ghost) else 0 for i in range(3))
+        for lvl in self.levels_of(fd.levels):
+            if (fd.name, lvl) in self.fields or not (self.min_level <= lvl <= self.max_level):
+                continue
+            nc = dom.ncells(lvl)
+            lay = FieldLayout(nd, tuple(nc[i] if i < nd else 1 for i in range(3)), ghost, (0, 0, 0), (0, 0, 0), (0, 0, 0), ld.dup_comm,
+                              ld.ghost_comm, localization="cell")
+            f = Field(fd.name, lvl, lay, self.ops, nslots, None, ())
+            if order is not None:
+                f.cell_bc = (BC_NEUMANN, None)
+            elif fd.bc is not None:
+                f.cell_bc = (BC_DIRICHLET, self._cell_program(fd.bc, lvl))
+            else:
+                f.cell_bc = None
+            self.fields[(fd.name, lvl)] = f
+
+    def _cell_program(self, e, lvl: Optional[int]):
+        """Expression program (examg_expr_t) of a point expression of a cell field: the cell-centre kernels evaluate it at the cell
+        centres (loops) or at the face centres (boundary values), so it may read vf_cellCenter_* / vf_boundaryCoord_* but not the
+        node position."""
+        from .lib import ExprC
+
+        for n in _walk(e):
+            if n and n[0] == "id" and isinstance(n[1], str) and re.match(r"^vf_(nodePosition|nodePos)_", n[1]):
+                raise Exa4Unsupported("%s in an expression of a cell field" % n[1])
+        key = ("cellexpr", repr(e), lvl)
+        if key not in self._fn_cache:
+            try:
+                self._fn_cache[key] = ExprC.from_program(self._compile_point_expr(e, lvl))
+            except ValueError as ex:
+                raise Exa4Unsupported(str(ex))
+        return self._fn_cache[key]
+
+    def _touches_cell(self, stmts) -> bool:
+        """Does any field access in these statements name a cell field?"""
+        if not self._cell_names:
+            return False
+        return any(n and n[0] == "fld" and n[1] in self._cell_names for n in _walk(("block", list(stmts))))
+
+    def _check_cell_body(self, body, fr: _Frame) -> bool:
+        """One loop body over cell fields (True) or node fields (False): never both, no node positions in a cell body and no cell
+        centres in a node body, and stencils with axis entries only beside cell fields (a cell stencil with entries off the axes
+        would read edge and corner ghosts, which examg_apply_bc_cell does not write)."""
+        nodes = [n for n in _walk(("block", list(body))) if n and isinstance(n[0], str)]
+        locs = {self._field(n, fr)[0].layout.localization for n in nodes if n[0] == "fld" and n[1] in self._cell_names} | \
+            {"node" for n in nodes if n[0] == "fld" and n[1] not in self._cell_names}
+        if len(locs) > 1:
+            raise Exa4Unsupported("cell and node fields mixed in one loop body")
+        cell = locs == {"cell"}
+        for n in nodes:
+            if cell and n[0] == "sten" and n[1] not in self.transfer:
+                A = self.stencil(n[1], self._level_of(n[2], fr))
+                if any(sum(1 for c in o if c) > 1 for o in A.offsets):
+                    raise Exa4Unsupported("stencil %s on a cell field has entries off the axes (edge / corner ghosts are not set)" % n[1])
+            if n[0] == "id" and isinstance(n[1], str):
+                if not cell and re.match(r"^vf_cellCent(er|re)_", n[1]):
+                    raise Exa4Unsupported("%s in a loop over node fields" % n[1])
+                if cell and re.match(r"^vf_(nodePosition|nodePos)_", n[1]):
+                    raise Exa4Unsupported("%s in a loop over cell fields" % n[1])
+        return cell
 
     def _apply_layout_transformations(self):
         """`LayoutTransformations { transform <field>@<levels> with [x, y, z, i] => [i, x, y, z] }` on the coefficient field of a
@@ -465,7 +565,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                 return math.pi
             m = _GRIDW.match(name)
             if m:
-                return self.domain.h(self._level_of(e[2], fr))["xyz".index(m.group(1))]
+                return self.domain.h(self._level_of(e[2], fr))["xyz".index(m.group(2))]
             m = _COORD.match(name)
             if m:
                 v = fr.vars.get("__" + m.group(2))
@@ -817,6 +917,13 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
             raise Exa4SyntaxError("statement %r" % (k,))
 
     def _apply_bc(self, f: Field, slot: int):
+        if f.layout.is_cell:
+            # a ghost value is a function of the interior: written every time, never assumed valid
+            mask = self.domain.face_mask()
+            if f.cell_bc is not None and mask:
+                self.launches += 1
+                self.ops.apply_bc_cell(f.lc, f.data(slot), self.domain.geom(f.level), f.cell_bc[0], f.cell_bc[1], mask)
+            return
         if f.bc_fn is None:
             return
         if self.fuse and (f.name, f.level, slot) in self._bc_valid:
@@ -901,6 +1008,10 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
     def _exec_loop(self, s, fr: _Frame):
         _, target, only, where, reduction, body = s
         f, _ = self._field(target, fr)
+        if self._check_cell_body(body, fr) and not f.layout.is_cell:
+            raise Exa4Unsupported("loop over node field %s with a body over cell fields" % f.name)
+        if f.layout.is_cell and (only is not None or fr.contract is not None):
+            raise Exa4Unsupported("loop over cell field %s: `only` regions and contraction" % f.name)
         boxes, colour = self._loop_boxes(f, only, where, reduction, fr)
         if reduction is not None:
             return self._exec_reduction(f, boxes, reduction, body, fr)
@@ -985,6 +1096,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
         if op == "=":
             if self._is_scalar(rhs):
                 return ops.set(D.lc, D.data(ds), float(self._eval(rhs, fr)), b, e)
+            if not _contains(rhs, ("fld", "sten", "sentry")) and D.layout.is_cell:
+                return ops.fill_expr_cell(D.lc, D.data(ds), self.domain.geom(D.level), self._cell_program(rhs, D.level), b, e)
             if not _contains(rhs, ("fld", "sten", "sentry")):
                 fn, par = self._analytic(rhs, D.level)
                 if isinstance(fn, int):
@@ -1001,6 +1114,13 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
             m = self._sten_times_field(rhs, fr)
             if m is not None:
                 X, xs = self._field(m[4], fr)
+                if m[1] in ("restriction", "cell_restriction") and (m[1] == "cell_restriction") != (X.layout.is_cell and D.layout.is_cell):
+                    raise Exa4Unsupported("%s restriction %s between %s and %s fields" % ("cell" if m[1][0] == "c" else "node", m[2],
+                                                                                          X.layout.localization, D.layout.localization))
+                if m[1] == "cell_restriction":
+                    if X.level != D.level + 1:
+                        raise Exa4Unsupported("restriction between levels %d and %d" % (X.level, D.level))
+                    return ops.restrict_cell(X.lc, X.data(xs), D.lc, D.data(ds), m[0], b, e)
                 if m[1] == "restriction":
                     if X.level != D.level + 1:
                         raise Exa4Unsupported("restriction between levels %d and %d" % (X.level, D.level))
@@ -1019,6 +1139,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                         return ops.axpby(X.lc, X.data(xs), D.lc, D.data(ds), 1.0, float(self._eval(t[2], fr)), b, e)
         elif op in ("+=", "-="):
             sign = 1.0 if op == "+=" else -1.0
+            if self._is_scalar(rhs):     # F += s | F -= s  (x + (-s) is exactly x - s)
+                return ops.add_scalar(D.lc, D.data(ds), sign * float(self._eval(rhs, fr)), b, e)
             if rhs[0] == "fld":          # x += y | x -= y  (y + (-1.0) * x is exactly y - x)
                 X, xs = self._field(rhs, fr)
                 return ops.axpby(X.lc, X.data(xs), D.lc, D.data(ds), sign, 1.0, b, e)
@@ -1030,6 +1152,15 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                 if r is not None and op == "+=" and self._same_access(lhs, r[2], fr):
                     return self._smooth(D, ds, lhs, rhs[2], r, b, e, colour, fr)
                 m = self._sten_times_field(rhs, fr)
+                if m is not None and m[1] in ("prolongation", "cell_prolongation") and op == "+=" and m[0] == 1.0:
+                    X, xs = self._field(m[4], fr)
+                    if (m[1] == "cell_prolongation") != (X.layout.is_cell and D.layout.is_cell):
+                        raise Exa4Unsupported("%s prolongation %s between %s and %s fields" % ("cell" if m[1][0] == "c" else "node", m[2],
+                                                                                               X.layout.localization, D.layout.localization))
+                if m is not None and m[1] == "cell_prolongation" and op == "+=" and m[0] == 1.0:
+                    if X.level != D.level - 1:
+                        raise Exa4Unsupported("prolongation between levels %d and %d" % (X.level, D.level))
+                    return ops.prolong_add_cell(X.lc, X.data(xs), D.lc, D.data(ds), b, e)
                 if m is not None and m[1] == "prolongation" and op == "+=" and m[0] == 1.0:
                     X, xs = self._field(m[4], fr)
                     if X.level != D.level - 1:
@@ -1061,6 +1192,14 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
             if st[0] != "assign" or st[2] != ("id", var, None):
                 raise Exa4Unsupported("reduction loop body")
             rhs = st[3]
+            if op == "+" and st[1] == "+=" and rhs[0] == "fld":           # s += F
+                X, xs = self._field(rhs, fr)
+                acc = 0.0
+                for b, e in boxes:
+                    self.launches += 1
+                    acc += self.comm.reduce_value(self.ops.sum(X.lc, X.data(xs), b, e), "sum")
+                fr.vars[var] = fr.vars[var] + acc
+                continue
             if op == "+" and st[1] == "+=" and rhs[0] == "bin" and rhs[1] == "*" and rhs[2][0] == "fld" and rhs[3][0] == "fld":
                 X, xs = self._field(rhs[2], fr)
                 Y, ys = self._field(rhs[3], fr)
@@ -1079,8 +1218,16 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                         t = locals_[t[1]]
                     if t[0] == "call" and t[1] in ("fabs", "abs") and t[3][0][0] == "bin" and t[3][0][1] == "-" and t[3][0][2][0] == "fld":
                         X, xs = self._field(t[3][0][2], fr)
-                        fn, par = self._analytic(t[3][0][3], X.level)
                         acc = fr.vars[var]
+                        if X.layout.is_cell:
+                            prog = self._cell_program(t[3][0][3], X.level)
+                            for b, e in boxes:
+                                self.launches += 1
+                                r = self.ops.max_err_expr_cell(X.lc, X.data(xs), self.domain.geom(X.level), prog, b, e)
+                                acc = max(acc, self.comm.reduce_value(r, "max"))
+                            fr.vars[var] = acc
+                            continue
+                        fn, par = self._analytic(t[3][0][3], X.level)
                         for b, e in boxes:
                             self.launches += 1
                             if isinstance(fn, int):

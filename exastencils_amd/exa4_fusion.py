@@ -49,8 +49,8 @@ class LazyFusions:
             return False
         op, lhs, rhs = st[1], st[2], st[3]
         D, ds = self._field(lhs, fr)
-        if D is not target or D.num_slots != 1 or D.layout.transform:
-            return False
+        if D is not target or D.num_slots != 1 or D.layout.transform or D.layout.is_cell or self._touches_cell([st]):
+            return False        # cell fields are never deferred: no one-pass form has their ghost updates
         b, e = box
         fb, fe = self.domain.loop_bounds(D.layout)
         if list(b) != list(fb) or list(e) != list(fe):

@@ -116,8 +116,8 @@ _MATH = {"sqrt": math.sqrt, "fabs": abs, "abs": abs, "sin": math.sin, "cos": mat
          "sinh": math.sinh, "cosh": math.cosh, "tanh": math.tanh, "log": math.log, "pow": math.pow, "max": max, "min": min,
          "floor": math.floor, "ceil": math.ceil, "ldexp": lambda x, e: math.ldexp(float(x), int(e)), "fmod": math.fmod,
          "asin": math.asin, "acos": math.acos, "atan": math.atan, "atan2": math.atan2, "log10": math.log10}
-_COORD = re.compile(r"^vf_(nodePosition|nodePos|boundaryCoord|boundaryPosition|boundaryPos)_([xyz])$")
-_GRIDW = re.compile(r"^vf_gridWidth_([xyz])$")
+_COORD = re.compile(r"^vf_(nodePosition|nodePos|boundaryCoord|boundaryPosition|boundaryPos|cellCenter|cellCentre)_([xyz])$")
+_GRIDW = re.compile(r"^vf_(gridWidth|cellWidth)_([xyz])$")
 
 
 # =====================================================================================================================
@@ -305,9 +305,9 @@ class Parser:
             loc = self.ident()
             self.expect("with")
             interp = self.next().text.strip("\"'")
-            if kind not in ("restriction", "prolongation") or loc != "Node" or interp != "linear":
+            if kind not in ("restriction", "prolongation") or loc not in ("Node", "Cell") or interp != "linear":
                 raise Exa4Unsupported("default %s on %s with %r" % (kind, loc, interp))
-            self.stencils.append(StencilDecl(name, None, [], kind))
+            self.stencils.append(StencilDecl(name, None, [], kind if loc == "Node" else "cell_" + kind))
             return
         levels = self.decl_levels()
         d = StencilDecl(name, levels)
@@ -748,12 +748,22 @@ def _arith(op: str, a, b):
 
 
 def _classify_transfer(mapped) -> str:
-    """`[i0, i1] from [2.0 * i0 - 1.0, ...] with w` entries: which inter-grid operator, and is it the linear one?"""
+    """`[i0, i1] from [2.0 * i0 - 1.0, ...] with w` entries: which inter-grid operator, and is it the linear one?
+    Node: 3^d entries, offsets in {-1, 0, 1} (restriction, weights kron [1/4 1/2 1/4]) or {-1/2, 0, 1/2} (prolongation, kron
+    [1/2 1 1/2]).  Cell (operator/l4/L4_DefaultRestriction.scala:37-43): 2^d entries, offsets 2i + {0, 1} and weights 0.5^d
+    (restriction: 'cell_restriction'), or the transpose times 2^d, offsets i/2 - {0, 1/2} and weights 1.0 ('cell_prolongation')."""
     env = {"i0": 0.0, "i1": 0.0, "i2": 0.0}
     offs = [tuple(float(_const_value(e, env)) for e in src) for src, _ in mapped]
     weights = [float(_const_value(w)) for _, w in mapped]
     prolong = any(abs(o) == 0.5 for off in offs for o in off)
     nd = len(offs[0])
+    if len(offs) == 2 ** nd:
+        allowed = (0.0, -0.5) if prolong else (0.0, 1.0)
+        ok = all(o in allowed for off in offs for o in off) and len(set(offs)) == len(offs)
+        want = 1.0 if prolong else 0.5 ** nd
+        if not ok or any(w != want for w in weights):
+            raise Exa4Unsupported("inter-grid stencil is not the linear cell %s" % ("prolongation" if prolong else "restriction"))
+        return "cell_prolongation" if prolong else "cell_restriction"
     if len(offs) != 3 ** nd:
         raise Exa4Unsupported("inter-grid stencil with %d entries in %dD" % (len(offs), nd))
     for off, w in zip(offs, weights):

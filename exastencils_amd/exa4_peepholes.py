@@ -39,6 +39,8 @@ class Peepholes:
         D, ds = self._field(lhs, fr)
         U, us = self._field(src, fr)
         F, fs = self._field(r[0], fr)
+        if D.layout.is_cell or U.layout.is_cell or F.layout.is_cell:
+            return None         # cell fields: ghost values depend on the interior after every step -- statement by statement
         wv, A = self._smoother_weight(wexpr, r[1], fr)
         if D.layout.transform or U.layout.transform or F.layout.transform:
             return None         # fields under a layout transformation: the plain loops (the kernel layer's one-pass forms take plain layouts)
@@ -54,6 +56,8 @@ class Peepholes:
         boundary shell, then the two arrays change roles.  `apply bc` re-writes position-only Dirichlet values the sweep
         never touches, so it is a no-op here."""
         multi = self.domain.world_size != 1
+        if self._touches_cell(body):
+            return False        # cell fields: a boundary update between the half sweeps (follow-up: fused passes for cell fields)
         if multi and not any(st[0] == "comm" and st[2] in ("all", "ghost") for st in body):
             return False        # blocks with neighbours: the fused form contains the exchanges of the statement list
         loops = [st for st in body if st[0] == "loop"]
@@ -130,6 +134,8 @@ class Peepholes:
         fb = fn.body
         if len(fb) != 3 or fb[0][0] != "comm" or fb[1][0] != "loop" or fb[2][0] != "advance":
             return False
+        if self._touches_cell(fb):
+            return False
         if fb[0][2] != "ghost":
             return False        # jacobi_pair exchanges ghost layers only: `communicate u` / `communicate dup of u` keep the plain path
         cfr = _Frame(lvl if fn.levels is not None else None, {})
@@ -177,6 +183,8 @@ class Peepholes:
         the box widened by e, second on the box widened by e - 1) -- the reference's own use of the construct
         (Testing/PolyExpl/Jac3Dcc.exa4:27: 5 ghost layers, 5 steps)."""
         _, nexpr, counter, pos, neg, body = s
+        if self._touches_cell(body):
+            raise Exa4Unsupported("repeat ... with contraction over cell fields")
         n = int(self._eval(nexpr, fr))
         if any(st[0] not in ("loop", "advance") for st in body):
             raise Exa4Unsupported("repeat ... with contraction: body may hold `loop over` and `advance` statements only")
@@ -311,8 +319,8 @@ class Peepholes:
         if self.domain.face_mask() != (1 << (2 * self.nd)) - 1:
             return None         # a periodic block is its own neighbour: the solver's `communicate` statements do something
         body = self._inline(fn.body, lvl)
-        if body is None:
-            return None
+        if body is None or self._touches_cell(body):
+            return None         # cell fields: the persistent solver sets node Dirichlet planes, not ghost cells
         fr = _Frame(lvl, {})
         pos = [0]
 

@@ -28,6 +28,30 @@ class FieldLayout:
     # `[x, y, z] => [x / 2, y, z, x % 2]` (Testing/LayoutTrafo/rbgs.exa4:2).  Regions, iterator coordinates and boxes stay those of the
     # untransformed layout; only where a value lives changes.
     transform: int = 0
+    # "node" | "cell": Python-side only.  The C struct is the same for both (a cell layout is the one without duplicate layers);
+    # the localization travels as the choice of entry point (examg_*_cell).
+    localization: str = "node"
+
+    @property
+    def is_cell(self) -> bool:
+        return self.localization == "cell"
+
+    @staticmethod
+    def cell(nd: int, ncells: Sequence[int], ghost: int, communicates_ghost: bool = True, align: int = 0) -> "FieldLayout":
+        """`Layout X< Real, Cell >`: no duplicate layers, inner = the cells (fragLen * 2^level per dimension).  `align`: pads x
+        (as FieldLayout.node does) so that the first inner cell and the row length are multiples of `align` doubles -- with
+        align = 2 the fine pair (2I, 2I+1) of every row of a cell field starts 16-byte aligned (the 16-byte form of
+        examg_restrict_cell / examg_prolong_add_cell)."""
+        inner = tuple(int(ncells[d]) if d < nd else 1 for d in range(3))
+        if any(i < 1 for i in inner):
+            raise ValueError("a Cell field needs at least one cell per dimension")
+        g = tuple(ghost if d < nd else 0 for d in range(3))
+        pl, pr = [0, 0, 0], [0, 0, 0]
+        if align:
+            pl[0] = (align - g[0] % align) % align
+            tot = pl[0] + g[0] + inner[0] + g[0]
+            pr[0] = (align - tot % align) % align
+        return FieldLayout(nd, inner, g, (0, 0, 0), tuple(pl), tuple(pr), True, communicates_ghost, localization="cell")
 
     @staticmethod
     def node(nd: int, ncells: Sequence[int], ghost: int, communicates_dup: bool = True,

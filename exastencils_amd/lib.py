@@ -80,12 +80,15 @@ SYMBOLS = [
     "examg_transform_stencilfield", "examg_transform_field", "examg_layout_size", "examg_comm_peer_release", "examg_residual_restrict_one_pass", "examg_residual_restrict_blocks", "examg_prolong_add_blocks",
     "examg_comm_create_peer", "examg_comm_peer_alloc", "examg_comm_peer_connect", "examg_comm_peer_slab_bytes",
     "examg_comm_peer_gather_bytes", "examg_comm_status",
+    "examg_sum", "examg_add_scalar", "examg_fill_expr_cell", "examg_max_err_expr_cell", "examg_apply_bc_cell", "examg_restrict_cell",
+    "examg_prolong_add_cell",
 ]
 
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 128
 EXCH_DUP, EXCH_GHOST, EXCH_ALL, EXCH_CONCURRENT_AXES = 1, 2, 3, 4
 PASS_TMP_PLANES_VALID = 8
+BC_DIRICHLET, BC_NEUMANN = 0, 1
 CG_ALPHA_FROM_NORM, CG_NO_BC, CG_ZERO_START = 1, 2, 4
 
 
@@ -190,6 +193,13 @@ def load(path=None):
     L.examg_comm_peer_gather_bytes.argtypes = [vp]
     L.examg_comm_peer_gather_bytes.restype = C.c_size_t
     L.examg_comm_status.argtypes = [vp, vp]
+    L.examg_sum.argtypes = [lp, vp, ip, ip, vp, vp, vp]
+    L.examg_add_scalar.argtypes = [lp, vp, C.c_double, ip, ip, vp]
+    L.examg_fill_expr_cell.argtypes = [lp, vp, gp, ep, ip, ip, vp]
+    L.examg_max_err_expr_cell.argtypes = [lp, vp, gp, ep, ip, ip, vp, vp, vp]
+    L.examg_apply_bc_cell.argtypes = [lp, vp, gp, C.c_int, ep, C.c_uint32, vp]
+    L.examg_restrict_cell.argtypes = [lp, vp, lp, vp, C.c_double, ip, ip, vp]
+    L.examg_prolong_add_cell.argtypes = [lp, vp, lp, vp, ip, ip, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("examg_version", "examg_last_error", "examg_device_count", "examg_reduce_work_bytes", "examg_exchange_workspace_bytes",
@@ -198,6 +208,9 @@ def load(path=None):
     if hasattr(L, "examg_debug_force_generic"):      # debug build only
         L.examg_debug_force_generic.argtypes = [C.c_int]
         L.examg_debug_force_generic.restype = C.c_int
+    if hasattr(L, "examg_debug_cell_narrow"):        # debug build only: the 8-byte form of the cell transfer kernels
+        L.examg_debug_cell_narrow.argtypes = [C.c_int]
+        L.examg_debug_cell_narrow.restype = C.c_int
     _libs[path] = L
     if path == LIB_PATH:
         _lib = L

@@ -207,6 +207,39 @@ class HipOps:
         check(self.L.examg_apply_dirichlet_expr(C.byref(l), self.ptr(x), C.byref(geom), C.byref(expr), int(face_mask), self._stream()),
               "examg_apply_dirichlet_expr")
 
+    def sum(self, l, x, begin, end, out=None):
+        """sum of x over the box on the device (examg_sum: examg_dot's reduction tree)"""
+        out = self.new_scalar() if out is None else out
+        check(self.L.examg_sum(C.byref(l), self.ptr(x), ivec(begin), ivec(end), self.ptr(out), self.ptr(self._work), self._stream()), "examg_sum")
+        return out
+
+    def add_scalar(self, l, x, c: float, begin, end):
+        check(self.L.examg_add_scalar(C.byref(l), self.ptr(x), float(c), ivec(begin), ivec(end), self._stream()), "examg_add_scalar")
+
+    # -- cell-centred fields ------------------------------------------------------------------------
+    def fill_expr_cell(self, l, x, geom, expr, begin, end):
+        check(self.L.examg_fill_expr_cell(C.byref(l), self.ptr(x), C.byref(geom), C.byref(expr), ivec(begin), ivec(end), self._stream()),
+              "examg_fill_expr_cell")
+
+    def max_err_expr_cell(self, l, x, geom, expr, begin, end, out=None):
+        out = self.new_scalar() if out is None else out
+        check(self.L.examg_max_err_expr_cell(C.byref(l), self.ptr(x), C.byref(geom), C.byref(expr), ivec(begin), ivec(end), self.ptr(out),
+                                             self.ptr(self._work), self._stream()), "examg_max_err_expr_cell")
+        return out
+
+    def apply_bc_cell(self, l, x, geom, kind: int, expr, face_mask: int):
+        """kind: lib.BC_DIRICHLET (expr: the boundary value at the face centres) or lib.BC_NEUMANN (expr may be None)."""
+        check(self.L.examg_apply_bc_cell(C.byref(l), self.ptr(x), C.byref(geom), int(kind), C.byref(expr) if expr is not None else None,
+                                         int(face_mask), self._stream()), "examg_apply_bc_cell")
+
+    def restrict_cell(self, lfine, rf, lc, fc, scale: float, begin, end):
+        check(self.L.examg_restrict_cell(C.byref(lfine), self.ptr(rf), C.byref(lc), self.ptr(fc), float(scale), ivec(begin), ivec(end),
+                                         self._stream()), "examg_restrict_cell")
+
+    def prolong_add_cell(self, lc, uc, lfine, uf, begin, end):
+        check(self.L.examg_prolong_add_cell(C.byref(lc), self.ptr(uc), C.byref(lfine), self.ptr(uf), ivec(begin), ivec(end), self._stream()),
+              "examg_prolong_add_cell")
+
     def scalar_value(self, t) -> float:
         """Host value of a device scalar (the reference's 8-byte D2H copy after a reduction)."""
         return float(t.item())

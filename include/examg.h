@@ -508,6 +508,54 @@ int examg_comm_status(examg_comm_t *comm, examg_stream_t stream);
 /* Deterministic synthetic field (SplitMix64 of the linear index, U(-1,1)); same bits as the oracle's. */
 int examg_fill_random(double *x, int64_t n, uint64_t seed, examg_stream_t stream);
 
+/* ---- Sum over a box and a scalar added over a box (any localization) ---------------------------------------------------
+ * examg_sum: *result = sum of x over [begin,end) -- `s += F` with `reduction (+ : s)`; the fixed reduction tree and the work
+ * buffer of examg_dot.  examg_add_scalar: x = x + c over the box -- `F += s`; `F -= s` is c = -s (x + (-s) is bitwise x - s). */
+int examg_sum(const examg_layout_t *l, const double *x, const int32_t *begin, const int32_t *end, double *result, void *work,
+              examg_stream_t stream);
+int examg_add_scalar(const examg_layout_t *l, double *x, double c, const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
+/* ---- Cell-centred fields (`Layout X< Real, Cell >`) ---------------------------------------------------------------------
+ * A cell layout has no duplicate layers (dup_l = dup_r = 0): inner = cells of the fragment, iterator index 0 is the first
+ * cell, `loop over` covers [0, inner) (baseExt/ir/IR_LoopOverPointsInOneFragment.scala, the IR_AtCellCenter case).  The
+ * layout struct is the node one; the localization is the choice of entry point.
+ * Positions: cell centre = (i * h + pos_begin) + 0.5 * h (grid/ir/IR_VF_CellCenter.scala:97-100).
+ *
+ * examg_fill_expr_cell / examg_max_err_expr_cell: examg_fill_expr / examg_max_err_expr with the program evaluated at the
+ * cell centres. */
+int examg_fill_expr_cell(const examg_layout_t *l, double *x, const examg_geom_t *g, const examg_expr_t *e, const int32_t *begin,
+                         const int32_t *end, examg_stream_t stream);
+int examg_max_err_expr_cell(const examg_layout_t *l, const double *x, const examg_geom_t *g, const examg_expr_t *e,
+                            const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream);
+
+/* `apply bc` of a cell field (boundary/ir/IR_ApplyBCFunction.scala:53-83): the ghost cell beside every boundary cell of each
+ * face in face_mask (bit 2*d + (side > 0)), all faces in ONE launch, order 1:
+ *   EXAMG_BC_DIRICHLET: ghost = 2.0 * g(face centre) - interior   (boundary/ir/IR_DirichletBC.scala, generateFieldUpdatesCell)
+ *   EXAMG_BC_NEUMANN  : ghost = interior                           (boundary/ir/IR_NeumannBC.scala, generateFieldUpdatesCell)
+ * g is the program `expr` (a constant is a one-instruction program; ignored for Neumann) evaluated at the face centre
+ * (boundary/ir/IR_HandleBoundaries.scala:55-70): the cell centre in the tangential dimensions, the node position of the face
+ * (index 0 below, index inner above) in the normal one.
+ * Edge and corner ghosts are NOT written: tangentially each face covers the inner cells only.  The reference handles the
+ * faces one after the other over a range that includes them; a cell stencil with entries off the axes would see the
+ * difference, which is why the interpreter refuses those (only axis entries read ghosts, and every axis ghost is written
+ * here exactly as the reference writes it).  Needs ghost >= 1 in every dimension of the mask. */
+enum { EXAMG_BC_DIRICHLET = 0, EXAMG_BC_NEUMANN = 1 };
+int examg_apply_bc_cell(const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
+                        uint32_t face_mask, examg_stream_t stream);
+
+/* RHS@coarser = scale * R * Residual with R the linear cell restriction (operator/l4/L4_DefaultRestriction.scala:37-43,63-90):
+ * kron over the dimensions of [2i -> 0.5, 2i+1 -> 0.5], the mean of the 2^d child cells, weight 0.5^d exactly.
+ *   fc(I) = sum over the children, in entry order of the composed stencil (x offset outermost, then y, then z),
+ *           of (scale * 0.5^d) * rf(2I + o)
+ * begin/end: coarse iterator box.  Reads no ghost cell. */
+int examg_restrict_cell(const examg_layout_t *lfine, const double *rf, const examg_layout_t *lcoarse, double *fc, double scale,
+                        const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
+/* Solution += P@coarser * Solution@coarser with P = 2^d R^T (operator/l4/L4_DefaultProlongation.scala:30-45): every fine cell
+ * receives 1.0 * its parent, uf(i) = uf(i) + uc(floor(i / 2)) -- piecewise-constant injection.  begin/end: fine iterator box. */
+int examg_prolong_add_cell(const examg_layout_t *lcoarse, const double *uc, const examg_layout_t *lfine, double *uf,
+                           const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1385,9 +1385,9 @@ extern "C" int examg_jacobi2(const examg_layout_t *lu, const double *u_in, doubl
   return examg_jacobi(lu, tmp, u_out, lf, rhs, st, w, begin, end, stream);
 }
 
-// Three Jacobi steps, u_in -> u_out on the box (u_out's planes outside the box are not written: the caller keeps boundary and ghost
-// values there, as for examg_jacobi2); one pass where k_three_stage7_lds applies, otherwise a step into `tmp` and a pair from there (or
-// three steps), for which `tmp` must be a distinct array.
+// Three Jacobi steps, u_in -> u_out on the box; one pass where k_three_stage7_lds applies (nothing outside the box is written), otherwise
+// a step into `tmp` and a pair from there (or three steps), for which `tmp` must be a distinct array.  The three-step form of that
+// fallback copies u_in's values to the box's one-stencil-reach shell of u_out first (include/examg.h).
 extern "C" int examg_jacobi3(const examg_layout_t *lu, const double *u_in, double *u_out, double *tmp, const examg_layout_t *lf,
                              const double *rhs, const examg_stencil_t *st, double w, const int32_t *begin, const int32_t *end,
                              examg_stream_t stream) {

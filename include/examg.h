@@ -136,7 +136,7 @@ int examg_rbgs_sweep_fused(const examg_layout_t *lu, const double *u_in, double 
 
 /* As examg_rbgs_sweep_fused with separate boxes, for blocks with neighbours: colour `first` on [begin1,end1) (points
  * outside keep u_in's value), then the other colour of that field on [begin2,end2), inside box 1; u_out receives both
- * colours on box 2 and is not touched elsewhere.  Box 1 = the loop's box shrunk by one point at interior faces, box 2 by
+ * colours on box 2 and is not touched elsewhere, on every path.  Box 1 = the loop's box shrunk by one point at interior faces, box 2 by
  * two: everything inside is independent of the halo exchange between the two half sweeps
  * (communicate inside `color with`, Benchmark/Poisson3D/3D_FD_Poisson_fromL4.exa4:204-213).  `tmp` is used by the fallback
  * path only (general stencils, short rows) and may be NULL otherwise. */
@@ -149,6 +149,7 @@ int examg_rbgs_sweep_fused_boxes(const examg_layout_t *lu, const double *u_in, d
  * sense of baseExt/ir/IR_ContractingLoop.scala.  u_out[box] = J(J(u_in)); bit-identical to two examg_jacobi calls
  * u_in -> tmp -> u_out.  Only valid when no halo exchange is needed between the two steps (single block, or ghost
  * layers two deep); `tmp` is used by the fallback path only (general stencils, small boxes) and may be NULL otherwise.
+ * Outside the box nothing of u_out is written, on every path (the fallback keeps the shell it needs in `tmp`).
  * One-pass forms exist for the 3-D 7-point constant stencil and for 27-entry stencil fields in the record layout
  * (EXAMG_CLAYOUT_ENTRY_FASTEST, entry order of examg_init_helmholtz27: the two steps of a point share its 216 B of coefficients). */
 int examg_jacobi2(const examg_layout_t *lu, const double *u_in, double *u_out, double *tmp, const examg_layout_t *lf,
@@ -159,7 +160,9 @@ int examg_jacobi2(const examg_layout_t *lu, const double *u_in, double *u_out, d
  * Testing/PolyExpl/Jac3Dcc.exa4:27 runs as 3 + 2; baseExt/ir/IR_ContractingLoop.scala:45-196): u_out[box] = J(J(J(u_in))), bit-identical
  * to three examg_jacobi calls.  Same conditions as examg_jacobi2 (no halo exchange needed in between); the one-pass form exists for the
  * 3-D 7-point constant stencil on rows of at least 64 points; otherwise a step into `tmp` and a pair from there (`tmp` must then be a
- * distinct array; NULL is allowed where the one-pass form applies). */
+ * distinct array; NULL is allowed where the one-pass form applies).  Outside the box: the one-pass form (examg_three_stage_eligible)
+ * writes nothing; so does the fallback where the pair after its first step runs in one pass (examg_two_stage_eligible with both
+ * boxes = [begin,end)); otherwise it copies u_in's values to the box's one-stencil-reach shell of u_out, and nothing further out. */
 int examg_jacobi3(const examg_layout_t *lu, const double *u_in, double *u_out, double *tmp, const examg_layout_t *lf,
                   const double *rhs, const examg_stencil_t *st, double w, const int32_t *begin, const int32_t *end,
                   examg_stream_t stream);
@@ -167,7 +170,9 @@ int examg_jacobi3(const examg_layout_t *lu, const double *u_in, double *u_out, d
 /* Three colour loops of a red-black smoother in ONE pass, out of place: colour `first`, the other colour, `first` again -- three sweeps
  * (`repeat 3 times { color with { ... } }`, Benchmark/Poisson3D/3D_FD_Poisson_fromL4.exa4:204-213) are two such passes, the second with
  * first = 1 - first.  u_out[box] = the three loops applied to u_in; bit-identical to three examg_rbgs_colour calls in place.  One-pass
- * form: 3-D 7-point constant stencil, rows of at least 64 points (examg_three_stage_eligible); otherwise a copy and the three loops. */
+ * form: 3-D 7-point constant stencil, rows of at least 64 points (examg_three_stage_eligible); otherwise a copy and the three loops.
+ * Outside the box: the one-pass form writes nothing; the fallback copies u_in's values to the box's one-stencil-reach shell of u_out
+ * and writes nothing further out. */
 int examg_rbgs_colours3(const examg_layout_t *lu, const double *u_in, double *u_out, const examg_layout_t *lf, const double *rhs,
                         const examg_stencil_t *st, double w, int first, const int32_t *begin, const int32_t *end, examg_stream_t stream);
 
@@ -180,7 +185,8 @@ int examg_three_stage_eligible(const examg_layout_t *lu, const examg_layout_t *l
  * Benchmark/Poisson3D/3D_FD_Poisson_fromL4.exa4:215-219).  27-entry stencil fields in the record layout (EXAMG_CLAYOUT_ENTRY_FASTEST,
  * entry order of examg_init_helmholtz27) share the 216 B of coefficients per point between the two loops; everything else runs
  * examg_jacobi, then examg_residual.  The residual reads the one-point shell of the box from u_in: bit-identical to those two calls
- * when u_out holds u_in's values there (the slots of a field after `apply bc` / `communicate`).  u_in != u_out. */
+ * when u_out holds u_in's values there (the slots of a field after `apply bc` / `communicate`).  u_in != u_out.  Outside the box
+ * nothing of u_out or res is written. */
 int examg_jacobi_residual(const examg_layout_t *lu, const double *u_in, double *u_out, const examg_layout_t *lf, const double *rhs,
                           const examg_layout_t *lr, double *res, const examg_stencil_t *st, double w, const int32_t *begin,
                           const int32_t *end, examg_stream_t stream);
@@ -188,7 +194,8 @@ int examg_jacobi_residual(const examg_layout_t *lu, const double *u_in, double *
 /* As examg_jacobi2 with separate boxes: stage 1 = J on [begin1,end1) (points outside keep u_in's value), stage 2 = J of
  * that field on [begin2,end2), inside box 1, written to u_out.  With block neighbours: box 1 = the loop's box, box 2 =
  * box 1 without the duplicate planes at interior faces, whose second step needs the neighbour's first-step values
- * (halo exchange of the intermediate field, then a thin single-step launch on those planes). */
+ * (halo exchange of the intermediate field, then a thin single-step launch on those planes).  u_out is written on box 2 only,
+ * on every path. */
 int examg_jacobi2_boxes(const examg_layout_t *lu, const double *u_in, double *u_out, double *tmp, const examg_layout_t *lf,
                         const double *rhs, const examg_stencil_t *st, double w, const int32_t *begin1, const int32_t *end1,
                         const int32_t *begin2, const int32_t *end2, examg_stream_t stream);
@@ -196,7 +203,8 @@ int examg_jacobi2_boxes(const examg_layout_t *lu, const double *u_in, double *u_
 /* examg_rbgs_sweep_fused for a u_in that is 0.0 everywhere, boundary planes included -- a coarse level's first pre-smoothing
  * sweep after `Solution@coarser = 0` (mgCycle, Benchmark/Poisson3D/3D_FD_Poisson_fromL4.exa4:225-229 followed by :204-213): u_in is
  * not passed and not read (16 B per point instead of 24, and the zeroing loop need not run), the arithmetic is the same
- * expression evaluated on the constant 0.0: bit-identical.  The shell of u_out is not written (fallback path: zeroed). */
+ * expression evaluated on the constant 0.0: bit-identical.  Outside the box: the one-pass kernels (examg_two_stage_eligible with
+ * both boxes = [begin,end)) write nothing; the fallback zeroes the box's one-stencil-reach shell of u_out. */
 int examg_rbgs_sweep_fused_zero(const examg_layout_t *lu, double *u_out, const examg_layout_t *lf, const double *rhs,
                                 const examg_stencil_t *st, double w, int first, const int32_t *begin, const int32_t *end,
                                 examg_stream_t stream);
@@ -207,7 +215,9 @@ int examg_rbgs_sweep_fused_zero(const examg_layout_t *lu, double *u_out, const e
  * separate read-modify-write loop over the fine field (16 B per point).  u_in is not modified; u_out receives on the box
  * exactly (bit for bit) what examg_prolong_add on u_in followed by examg_rbgs_sweep_fused / examg_jacobi2 would put there.
  * Single block only (the correction's `communicate` and the halo exchanges of the smoother must be empty).  Arguments that the
- * one-pass kernel does not take (examg_two_stage_eligible with both boxes = [begin,end)) run copy + the plain loops. */
+ * one-pass kernel does not take (examg_two_stage_eligible with both boxes = [begin,end)) run copy + the plain loops.  Outside the
+ * box: the one-pass kernels write nothing; the fallback of examg_rbgs_sweep_fused_prolong and of examg_jacobi2_prolong copies
+ * u_in's values to the box's one-stencil-reach shell of u_out and writes nothing further out. */
 int examg_rbgs_sweep_fused_prolong(const examg_layout_t *lu, const double *u_in, double *u_out, const examg_layout_t *lf,
                                    const double *rhs, const examg_stencil_t *st, double w, int first, const int32_t *begin,
                                    const int32_t *end, const examg_layout_t *lc, const double *uc, examg_stream_t stream);

@@ -1,0 +1,404 @@
+"""Asymmetric constant stencils, exact test data and an exact reference of the constant-stencil operations (test helper).
+
+Every stencil the reference programs declare is symmetric: the -x and +x coefficients are equal, and so are the y and z pairs.  A
+kernel that applies a coefficient to the mirror neighbour gives the same bits on such a stencil.  The stencils here have pairwise
+distinct coefficients (no two of them equal in magnitude for the 5- and 7-point stars) and come in several entry orders, the
+centre first or not.
+
+Exact data: small integer fields, coefficients that are multiples of 1/4 and a dyadic smoother weight.  Every product and every
+partial sum is then a dyadic rational with few bits, exactly representable in fp64: any correct implementation returns exactly the
+mathematical value, in any summation order, with or without FMA.  ExactOps computes that value in int64 fixed point with FRAC
+fractional bits, straight from the ExaSlang definitions (numpy slicing, no call into the oracle or the library), and asserts on every
+value it produces that the value -- and every partial sum of the terms it was summed from, in any order -- is exactly representable.
+
+The compositions at the end (jacobi2, rbgs_sweep, ...) are the one-pass entry points written as their loops, on any kernel layer
+that has stencil_op / restrict / prolong_add / axpby: on ExactOps they are the exact reference, on the oracle the bitwise one.
+Outside the box they write nothing, and they never modify their inputs.
+"""
+from fractions import Fraction
+
+import numpy as np
+
+from exastencils_amd.field import Stencil
+
+APPLY, RESIDUAL, SMOOTH = 0, 1, 2
+
+# -- stencils ------------------------------------------------------------------------------------------------------------------------
+_AX = {"c": (0, 0, 0), "-x": (-1, 0, 0), "+x": (1, 0, 0), "-y": (0, -1, 0), "+y": (0, 1, 0), "-z": (0, 0, -1), "+z": (0, 0, 1)}
+# entry orders: the two of the reference programs and two permutations with the centre elsewhere
+ORDERS7 = {
+    "mp": ["c", "-x", "+x", "-y", "+y", "-z", "+z"],
+    "pm": ["c", "+x", "-x", "+y", "-y", "+z", "-z"],
+    "perm_a": ["+y", "-z", "c", "-x", "+z", "+x", "-y"],
+    "perm_b": ["-z", "+x", "-y", "+z", "+y", "c", "-x"],
+}
+ORDERS5 = {
+    "mp": ["c", "-x", "+x", "-y", "+y"],
+    "pm": ["c", "+x", "-x", "+y", "-y"],
+    "perm_a": ["+y", "c", "-x", "-y", "+x"],
+    "perm_b": ["-x", "+y", "+x", "c", "-y"],
+}
+OFFSETS27 = [(a, b, c) for c in (-1, 0, 1) for b in (-1, 0, 1) for a in (-1, 0, 1)]
+ORDERS27 = {
+    "centre_first": [(0, 0, 0)] + [o for o in OFFSETS27 if o != (0, 0, 0)],
+    "perm": [OFFSETS27[i] for i in np.random.default_rng(2727).permutation(27)],
+}
+
+
+def _star(coef_of, order, names):
+    return Stencil([_AX[n] for n in names[order]], [float(coef_of[n]) for n in names[order]])
+
+
+def _distinct_magnitudes(cs):
+    m = [abs(c) for c in cs]
+    assert len(set(m)) == len(m), "stencil coefficients must be pairwise distinct in magnitude: %r" % (cs,)
+
+
+def convdiff7(shape, order="mp"):
+    """Anisotropic diffusion + a centred convection term (cell Peclet numbers 0.35, -0.2, 0.15) + a small reaction term on the grid
+    of `shape` cells: seven pairwise distinct coefficients, the diagonal dominant.  Not dyadic: for the bitwise comparisons."""
+    k, pe = (1.0, 0.6, 1.4), (0.35, -0.2, 0.15)
+    c = {}
+    diag = 0.0
+    for d, ax in enumerate("xyz"):
+        s = k[d] * float(shape[d]) ** 2
+        c["-" + ax], c["+" + ax] = -s * (1.0 + pe[d]), -s * (1.0 - pe[d])
+        diag = diag + 2.0 * s
+    c["c"] = 1.05 * diag
+    _distinct_magnitudes(list(c.values()))
+    return _star(c, order, ORDERS7)
+
+
+def convdiff5(shape, order="mp"):
+    """The 2-D analogue of convdiff7."""
+    k, pe = (1.0, 0.7), (0.3, -0.25)
+    c = {}
+    diag = 0.0
+    for d, ax in enumerate("xy"):
+        s = k[d] * float(shape[d]) ** 2
+        c["-" + ax], c["+" + ax] = -s * (1.0 + pe[d]), -s * (1.0 - pe[d])
+        diag = diag + 2.0 * s
+    c["c"] = 1.05 * diag
+    _distinct_magnitudes(list(c.values()))
+    return _star(c, order, ORDERS5)
+
+
+def random27(order="centre_first"):
+    """27 distinct coefficients (not dyadic), the diagonal dominant."""
+    rng = np.random.default_rng(27)
+    off = {o: -float(v) for o, v in zip([o for o in OFFSETS27 if o != (0, 0, 0)], rng.uniform(0.1, 1.3, 26))}
+    off[(0, 0, 0)] = 1.1 * sum(-v for v in off.values())
+    offs = ORDERS27[order]
+    st = Stencil(offs, [off[o] for o in offs])
+    assert len(set(st.coefs)) == 27
+    return st
+
+
+# exact data: multiples of 1/4 with |c| <= 8, pairwise distinct in magnitude, the diagonal dominant
+EXACT7 = {"c": 7.5, "-x": -2.25, "+x": 0.5, "-y": -1.25, "+y": -0.75, "-z": -1.5, "+z": -0.25}
+EXACT5 = {"c": 6.0, "-x": -1.75, "+x": 0.5, "-y": -1.25, "+y": -0.25}
+# integer coefficients (residual_norm2: integer residuals, their squares summed exactly)
+INT7 = {"c": 8.0, "-x": -3.0, "+x": 1.0, "-y": -2.0, "+y": -4.0, "-z": 5.0, "+z": -6.0}
+EXACT_W = 1.0 / 16.0         # a dyadic smoother weight, not omega / diag for any omega of the programs
+
+
+def exact7(order="mp", coefs=EXACT7):
+    _distinct_magnitudes(list(coefs.values()))
+    return _star(coefs, order, ORDERS7)
+
+
+def exact5(order="mp"):
+    _distinct_magnitudes(list(EXACT5.values()))
+    return _star(EXACT5, order, ORDERS5)
+
+
+def exact27(order="centre_first"):
+    """27 distinct multiples of 1/4 (the off-diagonal ones +-1/4 .. +-13/4), centre 8."""
+    vals = [0.25 * s * m for m in range(1, 14) for s in (1, -1)]
+    perm = np.random.default_rng(2028).permutation(26)
+    others = [o for o in OFFSETS27 if o != (0, 0, 0)]
+    off = {o: vals[int(p)] for o, p in zip(others, perm)}
+    off[(0, 0, 0)] = 8.0
+    offs = ORDERS27[order]
+    st = Stencil(offs, [off[o] for o in offs])
+    assert len(set(st.coefs)) == 27
+    return st
+
+
+def is_star(st):
+    return all(sum(1 for v in o if v != 0) <= 1 and all(abs(v) <= 1 for v in o) for o in st.offsets)
+
+
+def free_weight(st):
+    """A smoother weight for the bitwise comparisons that is not 0.8 / diag (what every program passes)."""
+    return 0.713 / st.diag
+
+
+def int_field(size, seed, lo=-16, hi=16):
+    """Small integers from a seeded generator, as float64 (the whole allocation: ghost, duplicate and pad points included)."""
+    return np.random.default_rng(seed).integers(lo, hi + 1, size=int(size)).astype(np.float64)
+
+
+# -- exact reference ----------------------------------------------------------------------------------------------------------------
+FRAC = 32                    # fractional bits of the fixed-point values
+_LIM = 1 << 53               # |value| * 2^FRAC below this: a multiple of 2^-FRAC below 2^(53 - FRAC) in magnitude is exact in fp64
+
+
+class _Lay:
+    """Regions of a layout (a LayoutC or a FieldLayout), the index arithmetic of the ExaSlang field layout."""
+
+    def __init__(self, l):
+        if hasattr(l, "c_struct"):
+            l = l.c_struct()
+        if int(getattr(l, "transform", 0)) != 0:
+            raise ValueError("the exact reference works on untransformed layouts")
+        self.nd = int(l.nd)
+        self.ref = [int(l.pad_l[d]) + int(l.ghost_l[d]) for d in range(3)]
+        self.tot = [sum(int(getattr(l, k)[d]) for k in ("pad_l", "ghost_l", "dup_l", "inner", "dup_r", "ghost_r", "pad_r"))
+                    for d in range(3)]
+
+    @property
+    def shape(self):
+        return (self.tot[2], self.tot[1], self.tot[0])
+
+    def box(self, b, e, off=(0, 0, 0), step=1):
+        """numpy index of the iterator box [b, e) shifted by `off` (step 2: the points 2I + off of the coarse box I in [b, e))."""
+        sl = []
+        for d in (2, 1, 0):
+            lo = step * b[d] + off[d] + self.ref[d]
+            hi = step * (e[d] - 1) + off[d] + self.ref[d] + 1
+            if lo < 0 or hi > self.tot[d]:
+                raise IndexError("box %r..%r + %r leaves the allocation in dim %d" % (b, e, off, d))
+            sl.append(slice(lo, hi, step))
+        return tuple(sl)
+
+
+def _dyadic(c):
+    f = Fraction(c)            # every float is a dyadic rational: m / 2^k
+    return int(f.numerator), f.denominator.bit_length() - 1
+
+
+def _check(v):
+    if v.size and int(np.abs(v).max()) >= _LIM:
+        raise AssertionError("exact reference: a value leaves the exactly representable range (%.3g)" % (float(np.abs(v).max()) / 2.0 ** FRAC))
+    return v
+
+
+def _mul(v, c):
+    m, k = _dyadic(c)
+    if k > FRAC:
+        raise ValueError("exact reference: coefficient %r needs more fractional bits than %d" % (c, FRAC))
+    if v.size and int(np.abs(v).max()) * abs(m) >= _LIM:
+        raise AssertionError("exact reference: product leaves the exactly representable range")
+    p = v * m
+    if k and np.any(p & ((1 << k) - 1)):
+        raise AssertionError("exact reference: %d fractional bits are not enough" % FRAC)
+    return p >> k
+
+
+def _sum(terms):
+    """The exact sum; every partial sum in any order is bounded by the sum of the magnitudes, which must stay representable."""
+    _check(sum(np.abs(t) for t in terms))
+    return sum(terms[1:], terms[0].copy())
+
+
+class ExactOps:
+    """Kernel layer of exact values: arrays are int64 fixed point (value * 2^FRAC), layouts LayoutC or FieldLayout, stencils with
+    dyadic coefficients.  Same method signatures as the HIP and oracle kernel layers, for the calls the tests make."""
+
+    name = "exact"
+
+    def new_array(self, n):
+        return np.zeros(int(n), dtype=np.int64)
+
+    def from_host(self, a):
+        a = np.asarray(a, dtype=np.float64).reshape(-1)
+        v = np.ldexp(a, FRAC)
+        if not np.array_equal(v, np.round(v)):
+            raise ValueError("exact data needs multiples of 2^-%d" % FRAC)
+        return _check(v.astype(np.int64))
+
+    def to_host(self, t):
+        return np.ldexp(t.astype(np.float64), -FRAC)
+
+    def clone(self, t):
+        return t.copy()
+
+    def synchronize(self):
+        pass
+
+    @staticmethod
+    def _v(t, l):
+        return t.reshape(_Lay(l).shape)
+
+    def stencil_op(self, mode, lu, u, lf, rhs, ld, dst, st, w, colour, begin, end):
+        if st.cfield is not None:
+            raise ValueError("constant stencils only")
+        Lu, Ld = _Lay(lu), _Lay(ld)
+        U, D = self._v(u, lu), self._v(dst, ld)
+        acc = _sum([_mul(U[Lu.box(begin, end, o)], c) for o, c in zip(st.offsets, st.coefs)])
+        if mode == APPLY:
+            out = acc
+        else:
+            F = self._v(rhs, lf)[_Lay(lf).box(begin, end)]
+            out = _check(F - acc)
+            if mode == SMOOTH:
+                out = _check(U[Lu.box(begin, end)] + _check(_mul(out, w)))
+        db = Ld.box(begin, end)
+        if colour < 0:
+            D[db] = out
+            return
+        if u is dst and not is_star(st):
+            raise ValueError("an in-place colour loop of a stencil that reaches its own colour depends on the loop order")
+        i2, i1, i0 = np.meshgrid(*[np.arange(begin[d], end[d]) for d in (2, 1, 0)], indexing="ij")
+        D[db] = np.where((i0 + i1 + i2) % 2 == colour, out, D[db])
+
+    def restrict(self, lfine, rf, lc, fc, scale, begin, end):
+        Lf, Lc = _Lay(lfine), _Lay(lc)
+        R = self._v(rf, lfine)
+        w1 = {-1: 0.25, 0: 0.5, 1: 0.25}
+        nd = Lf.nd
+        offs = [(a, b, c) for a in (-1, 0, 1) for b in (-1, 0, 1) for c in ((-1, 0, 1) if nd == 3 else (0,))]
+        terms = []
+        for o in offs:
+            wgt = w1[o[0]] * w1[o[1]] * (w1[o[2]] if nd == 3 else 1.0)
+            terms.append(_mul(R[Lf.box(begin, end, (o[0], o[1], o[2] if nd == 3 else 0), step=2)], scale * wgt))
+        self._v(fc, lc)[Lc.box(begin, end)] = _sum(terms)
+
+    def prolong_add(self, lc, uc, lfine, uf, begin, end):
+        Lc, Lf = _Lay(lc), _Lay(lfine)
+        Uc, Uf = self._v(uc, lc), self._v(uf, lfine)
+        lo, hi = [], []
+        for d in range(3):
+            i = np.arange(begin[d], end[d])
+            if d < Lf.nd:
+                lo.append(i // 2 + Lc.ref[d])
+                hi.append((i + 1) // 2 + Lc.ref[d])
+            else:
+                lo.append(i + Lc.ref[d])
+                hi.append(i + Lc.ref[d])
+        for d in range(3):
+            if lo[d].size and (lo[d].min() < 0 or hi[d].max() >= Lc.tot[d]):
+                raise IndexError("coarse footprint leaves the allocation")
+        # per dimension 1/2 (c[lo] + c[hi]): weight 1 on an even index (lo == hi), 1/2 + 1/2 on an odd one
+        terms = []
+        for sx in (lo[0], hi[0]):
+            for sy in (lo[1], hi[1]):
+                for sz in (lo[2], hi[2]):
+                    terms.append(_mul(Uc[np.ix_(sz, sy, sx)], 0.125))
+        fb = Lf.box(begin, end)
+        Uf[fb] = _check(Uf[fb] + _sum(terms))
+
+    def axpby(self, lx, x, ly, y, a, b, begin, end):
+        Lx, Ly = _Lay(lx), _Lay(ly)
+        X, Y = self._v(x, lx), self._v(y, ly)
+        yb = Ly.box(begin, end)
+        Y[yb] = _sum([_mul(X[Lx.box(begin, end)], a), _mul(Y[yb], b)])
+
+    def residual_norm2(self, lu, u, lf, rhs, st, begin, end, lr=None, res=None, out=None):
+        """sum over the box of (rhs - A u)^2 as a float: the residuals must be integers here (their squares are summed exactly)."""
+        r = self.new_array(u.size)
+        self.stencil_op(RESIDUAL, lu, u, lf, rhs, lu, r, st, 0.0, -1, begin, end)
+        v = r.reshape(_Lay(lu).shape)[_Lay(lu).box(begin, end)]
+        if np.any(v & ((1 << FRAC) - 1)):
+            raise ValueError("residual_norm2 of the exact reference needs integer residuals")
+        iv = v >> FRAC
+        s = int(np.sum(iv * iv))
+        assert s < _LIM
+        return float(s)
+
+
+# -- the one-pass entry points as their loops (any kernel layer with the loops above; box-only writes, inputs untouched) -------
+def _clone(P, t):
+    return P.clone(t) if hasattr(P, "clone") else t.clone()
+
+
+def _zeros_like(P, t):
+    return P.new_array(t.numel() if hasattr(t, "numel") else t.size)
+
+
+def jacobi2(P, lu, u_in, u_out, lf, rhs, st, w, b, e):
+    t = _clone(P, u_in)
+    P.stencil_op(SMOOTH, lu, u_in, lf, rhs, lu, t, st, w, -1, b, e)
+    P.stencil_op(SMOOTH, lu, t, lf, rhs, lu, u_out, st, w, -1, b, e)
+
+
+def jacobi3(P, lu, u_in, u_out, lf, rhs, st, w, b, e):
+    t1, t2 = _clone(P, u_in), _clone(P, u_in)
+    P.stencil_op(SMOOTH, lu, u_in, lf, rhs, lu, t1, st, w, -1, b, e)
+    P.stencil_op(SMOOTH, lu, t1, lf, rhs, lu, t2, st, w, -1, b, e)
+    P.stencil_op(SMOOTH, lu, t2, lf, rhs, lu, u_out, st, w, -1, b, e)
+
+
+def jacobi2_boxes(P, lu, u_in, u_out, lf, rhs, st, w, b1, e1, b2, e2):
+    t = _clone(P, u_in)
+    P.stencil_op(SMOOTH, lu, u_in, lf, rhs, lu, t, st, w, -1, b1, e1)
+    P.stencil_op(SMOOTH, lu, t, lf, rhs, lu, u_out, st, w, -1, b2, e2)
+
+
+def jacobi2_prolong(P, lu, u_in, u_out, lf, rhs, st, w, b, e, lc, uc):
+    work = _clone(P, u_in)
+    P.prolong_add(lc, uc, lu, work, b, e)
+    jacobi2(P, lu, work, u_out, lf, rhs, st, w, b, e)
+
+
+def colours(P, lu, u_in, u_out, lf, rhs, st, w, cols, b, e, correction=None):
+    """The colour loops `cols` in place on a copy of u_in (optionally after `u += P uc`); u_out receives the box."""
+    work = _clone(P, u_in)
+    if correction is not None:
+        P.prolong_add(correction[0], correction[1], lu, work, b, e)
+    for c in cols:
+        P.stencil_op(SMOOTH, lu, work, lf, rhs, lu, work, st, w, c, b, e)
+    P.axpby(lu, work, lu, u_out, 1.0, 0.0, b, e)
+
+
+def rbgs_sweep(P, lu, u_in, u_out, lf, rhs, st, w, first, b, e):
+    colours(P, lu, u_in, u_out, lf, rhs, st, w, (first, 1 - first), b, e)
+
+
+def rbgs_sweep_zero(P, lu, u_out, lf, rhs, st, w, first, b, e):
+    colours(P, lu, _zeros_like(P, u_out), u_out, lf, rhs, st, w, (first, 1 - first), b, e)
+
+
+def rbgs_sweep_prolong(P, lu, u_in, u_out, lf, rhs, st, w, first, b, e, lc, uc):
+    colours(P, lu, u_in, u_out, lf, rhs, st, w, (first, 1 - first), b, e, (lc, uc))
+
+
+def rbgs_colours3(P, lu, u_in, u_out, lf, rhs, st, w, first, b, e):
+    colours(P, lu, u_in, u_out, lf, rhs, st, w, (first, 1 - first, first), b, e)
+
+
+def rbgs_sweep_boxes(P, lu, u_in, u_out, lf, rhs, st, w, first, b1, e1, b2, e2):
+    t = _clone(P, u_in)
+    P.stencil_op(SMOOTH, lu, t, lf, rhs, lu, t, st, w, first, b1, e1)
+    P.axpby(lu, t, lu, u_out, 1.0, 0.0, b2, e2)
+    P.stencil_op(SMOOTH, lu, t, lf, rhs, lu, u_out, st, w, 1 - first, b2, e2)
+
+
+def jacobi_residual(P, lu, u_in, u_out, lf, rhs, lr, res, st, w, b, e):
+    P.stencil_op(SMOOTH, lu, u_in, lf, rhs, lu, u_out, st, w, -1, b, e)
+    P.stencil_op(RESIDUAL, lu, u_out, lf, rhs, lr, res, st, 0.0, -1, b, e)
+
+
+def residual_restrict(P, lu, u, lf, rhs, st, lc, fc, scale, fb, fe, cb, ce):
+    r = _zeros_like(P, u)
+    P.stencil_op(RESIDUAL, lu, u, lf, rhs, lu, r, st, 0.0, -1, fb, fe)
+    P.restrict(lu, r, lc, fc, scale, cb, ce)
+
+
+def shell_mask(l, b, e, reach=1):
+    """Flat boolean mask of the points within `reach` of the box [b, e) but outside it (the dimensions of the layout only)."""
+    L = _Lay(l)
+    m = np.zeros(L.shape, dtype=bool)
+    bb = [b[d] - (reach if d < L.nd else 0) for d in range(3)]
+    ee = [e[d] + (reach if d < L.nd else 0) for d in range(3)]
+    m[L.box(bb, ee)] = True
+    m[L.box(b, e)] = False
+    return m.reshape(-1)
+
+
+def box_mask(l, b, e):
+    L = _Lay(l)
+    m = np.zeros(L.shape, dtype=bool)
+    m[L.box(b, e)] = True
+    return m.reshape(-1)

@@ -1,0 +1,525 @@
+"""Every constant-stencil entry point of libexamg on asymmetric stencils (tests/stencil_cases.py): pairwise distinct coefficients,
+the two entry orders of the reference programs and two permuted ones, free smoother weights, padded and deep-halo layouts, boxes on
+either side of the dispatch bounds.  Each case runs twice:
+
+  (a) random data, compared bit for bit with the oracle's loops over the whole output array;
+  (b) exact data, compared with equality against the exact reference -- independent of the summation order.
+
+Outside the box the one-pass kernels write nothing; the fallbacks that include/examg.h names write u_in's values to the box's
+one-stencil-reach shell of u_out.  The whole array is compared, the inputs included."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import stencil_cases as S
+from oracle_ops import OracleOps
+from stencil_cases import APPLY, RESIDUAL, SMOOTH, ExactOps
+from test_gpu_kernels import hip, hip3, hipd, two_stage_variant  # noqa: F401  (fixtures)
+
+from exastencils_amd.layout import FieldLayout
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def orc():
+    return OracleOps()
+
+
+@pytest.fixture(scope="module")
+def ex():
+    return ExactOps()
+
+
+# -- cases ------------------------------------------------------------------------------------------------------------------------
+def stencil(kind, order, data, shape):
+    """kind 7 / 5 / 27 / int7 (integer coefficients: residual norms); data 'random' (bitwise against the oracle) or 'exact'."""
+    if data == "exact":
+        return {"7": lambda: S.exact7(order), "5": lambda: S.exact5(order), "27": lambda: S.exact27(order),
+                "int7": lambda: S.exact7(order, S.INT7)}[kind]()
+    return {"7": lambda: S.convdiff7(shape, order), "5": lambda: S.convdiff5(shape, order), "27": lambda: S.random27(order),
+            "int7": lambda: S.convdiff7(shape, order)}[kind]()
+
+
+def weight(st, data):
+    return S.EXACT_W if data == "exact" else S.free_weight(st)
+
+
+def layouts(nd, shape, lay):
+    """(u layout, rhs layout): plain, padded (align 2 / 16), or u with two ghost layers and rhs with one (the deep-halo runs)."""
+    g, gf, align = (2, 1, 0) if lay == "halo2" else (1, 0, {"plain": 0, "align2": 2, "align16": 16}[lay])
+    return FieldLayout.node(nd, shape, g, align=align), FieldLayout.node(nd, shape, gf, True, False, align)
+
+
+def box(nd, shape, which):
+    """inner; dup: over the duplicate planes (a block with neighbours on every face); odd: inside the inner points, odd origins."""
+    z = nd == 3
+    if which == "inner":
+        return [1, 1, 1 if z else 0], [shape[0], shape[1], shape[2] if z else 1]
+    if which == "dup":
+        return [0, 0, 0], [shape[0] + 1, shape[1] + 1, shape[2] + 1 if z else 1]
+    return [3, 1, 3 if z else 0], [shape[0] - 2, shape[1] - 1, shape[2] - 1 if z else 1]
+
+
+def fields(ops, data, lays, seed):
+    """One array per layout: fill_random (same bits on both kernel layers) or small integers."""
+    out = []
+    for i, l in enumerate(lays):
+        if data == "exact":
+            out.append(ops.from_host(S.int_field(l.size, seed + i)))
+        else:
+            t = ops.new_array(l.size)
+            ops.fill_random(t, seed + i)
+            out.append(t)
+    return out
+
+
+def ref_ops(data, orc, ex):
+    return ex if data == "exact" else orc
+
+
+def host(ops, ts):
+    ops.synchronize()
+    return [np.array(ops.to_host(t), dtype=np.float64, copy=True) for t in ts]
+
+
+def assert_same(got, want, what):
+    for i, (g, w) in enumerate(zip(got, want)):
+        if not np.array_equal(g, w):
+            d = np.abs(g - w)
+            raise AssertionError("%s[%d]: %d of %d values differ, max abs %.3e" % (what, i, int((d > 0).sum()), d.size, np.nanmax(d)))
+
+
+def with_shell(want_out, u_in, lu, b, e, reach):
+    """The fallback's writes outside the box: u_in's values on the one-stencil-reach shell."""
+    m = S.shell_mask(lu, b, e, reach)
+    w = want_out.copy()
+    w[m] = u_in[m]
+    return w
+
+
+def reach(st):
+    return max(abs(v) for o in st.offsets for v in o)
+
+
+DATA = ["random", "exact"]
+ALIGN = {"plain": 0, "align2": 2, "align16": 16, "halo2": 0}
+
+
+# -- stencil_op: every path ---------------------------------------------------------------------------------------------------------
+# (path, nd, cells, layout, box, stencil kind, entry orders)
+STENCIL_CASES = [
+    ("rowmarch", 3, (420, 70, 17), "plain", "inner", "7", ("mp", "pm")),        # rows of 419 points: the row-marching kernel
+    ("rowmarch", 3, (420, 66, 18), "halo2", "dup", "7", ("pm",)),
+    ("zmarch", 3, (130, 40, 24), "plain", "inner", "7", ("mp", "pm")),
+    ("zmarch", 3, (65, 21, 9), "align16", "inner", "7", ("mp", "pm")),          # rows of 64 points: the lowest z-march row
+    ("zmarch", 3, (96, 30, 12), "align2", "odd", "7", ("pm",)),
+    ("zmarch", 3, (131, 24, 10), "halo2", "dup", "7", ("mp",)),
+    ("generic", 3, (96, 30, 12), "plain", "inner", "7", ("mp", "pm", "perm_a", "perm_b")),    # debug build: forced generic kernel
+    ("generic", 3, (40, 20, 12), "align16", "odd", "27", ("centre_first", "perm")),
+    ("perm", 3, (130, 40, 24), "plain", "inner", "7", ("perm_a", "perm_b")),    # long rows, permuted orders: the generic kernel
+    ("short", 3, (64, 20, 14), "plain", "inner", "7", ("mp", "pm", "perm_a")),  # rows of 63 points
+    ("short", 3, (33, 19, 9), "halo2", "dup", "7", ("pm", "perm_b")),
+    ("2d", 2, (257, 40, 0), "plain", "inner", "5", ("mp", "pm", "perm_a", "perm_b")),
+    ("2d", 2, (60, 30, 0), "align2", "odd", "5", ("mp", "perm_b")),
+    ("27", 3, (70, 20, 12), "plain", "inner", "27", ("centre_first", "perm")),
+]
+
+
+def _stencil_op_run(ops, data, lu, lf, st, w, mode, colour, b, e, in_place, seed):
+    u, f, d = fields(ops, data, (lu, lf, lu), seed)
+    dst = u if in_place else d
+    ops.stencil_op(mode, lu.c_struct(), u, lf.c_struct(), f, lu.c_struct(), dst, st, w, colour, b, e)
+    return [u, f, d]
+
+
+@pytest.mark.parametrize("data", DATA)
+@pytest.mark.parametrize("case", STENCIL_CASES, ids=lambda c: "%s-%s-%s-%s" % (c[0], c[3], c[4], c[5]))
+def test_stencil_op_paths(hip, hipd, orc, ex, case, data):
+    """examg_stencil_op, APPLY / RESIDUAL / SMOOTH with colours -1, 0, 1 (27 points: colour loops out of place), on every kernel it
+    dispatches to; the whole u, rhs and destination arrays."""
+    path, nd, shape, lay, which, kind, orders = case
+    lu, lf = layouts(nd, shape, lay)
+    b, e = box(nd, shape, which)
+    gpu = hipd if path == "generic" else hip
+    R = ref_ops(data, orc, ex)
+    if path == "generic":
+        old = hipd.L.examg_debug_force_generic(1)
+    try:
+        for order in orders:
+            st = stencil(kind, order, data, shape)
+            w = weight(st, data)
+            for mode in (APPLY, RESIDUAL, SMOOTH):
+                for colour in ((-1, 0, 1) if mode == SMOOTH else (-1,)):
+                    in_place = colour >= 0 and kind != "27"
+                    g = host(gpu, _stencil_op_run(gpu, data, lu, lf, st, w, mode, colour, b, e, in_place, 100))
+                    r = host(R, _stencil_op_run(R, data, lu, lf, st, w, mode, colour, b, e, in_place, 100))
+                    assert_same(g, r, "%s %s, mode %d colour %d" % (path, order, mode, colour))
+    finally:
+        if path == "generic":
+            hipd.L.examg_debug_force_generic(old)
+
+
+@pytest.mark.parametrize("data", DATA)
+@pytest.mark.parametrize("shape,kind,orders", [((200, 12, 40), "7", ("mp", "pm", "perm_a")), ((33, 17, 9), "7", ("pm",)),
+                                               ((64, 48, 0), "5", ("mp", "perm_b"))])
+def test_stencil_op_on_split_fields(hip, orc, ex, shape, kind, orders, data):
+    """The colour-split layout (half sweeps: k_rbgs_half_split7 for the canonical orders, the generic kernel otherwise), transformed
+    back: the reference's loop on the plain layout."""
+    nd = 2 if kind == "5" else 3
+    lu, lf = layouts(nd, shape, "plain")
+    b, e = box(nd, shape, "inner")
+    R = ref_ops(data, orc, ex)
+    for order in orders:
+        st = stencil(kind, order, data, shape)
+        w = weight(st, data)
+        for mode, colour in ((SMOOTH, 0), (SMOOTH, 1), (SMOOTH, -1), (RESIDUAL, -1), (APPLY, -1)):
+            in_place = colour >= 0
+            u, f, d = fields(hip, data, (lu, lf, lu), 200)
+            us, fs, ds = [hip.new_array(l.split_x().size) for l in (lu, lf, lu)]
+            for x, xs, l in ((u, us, lu), (f, fs, lf), (d, ds, lu)):
+                hip.transform_field(l.c_struct(), x, l.split_x().c_struct(), xs)
+            Su, Sf = lu.split_x().c_struct(), lf.split_x().c_struct()
+            hip.stencil_op(mode, Su, us, Sf, fs, Su, us if in_place else ds, st, w, colour, b, e)
+            for x, xs, l in ((u, us, lu), (d, ds, lu)):
+                hip.transform_field(l.split_x().c_struct(), xs, l.c_struct(), x)
+            g = host(hip, (u, f, d))
+            r = host(R, _stencil_op_run(R, data, lu, lf, st, w, mode, colour, b, e, in_place, 200))
+            assert_same(g, r, "split %s mode %d colour %d" % (order, mode, colour))
+
+
+@pytest.mark.parametrize("data", DATA)
+@pytest.mark.parametrize("n", [(64, 24, 16), (40, 20, 10)])
+def test_stencil_op_on_cell_layouts(hip, orc, ex, n, data):
+    """A cell layout (no duplicate layers, loop bounds [0, inner)): the layout-generic kernels."""
+    lu, lf = FieldLayout.cell(3, n, 1, align=2), FieldLayout.cell(3, n, 0)
+    b, e = [0, 0, 0], list(n)
+    R = ref_ops(data, orc, ex)
+    for order in ("pm", "perm_a"):
+        st = stencil("7", order, data, n)
+        w = weight(st, data)
+        for mode in (APPLY, RESIDUAL, SMOOTH):
+            for colour in ((-1, 1) if mode == SMOOTH else (-1,)):
+                g = host(hip, _stencil_op_run(hip, data, lu, lf, st, w, mode, colour, b, e, colour >= 0, 300))
+                r = host(R, _stencil_op_run(R, data, lu, lf, st, w, mode, colour, b, e, colour >= 0, 300))
+                assert_same(g, r, "cell %s mode %d colour %d" % (order, mode, colour))
+
+
+# -- one-pass sweeps and Jacobi pairs ------------------------------------------------------------------------------------------------
+# (cells, layout, box, stencil kind, order, path): path = the kernel examg_two_stage_eligible promises (two-stage / small / fallback)
+SWEEP_CASES = [
+    ((130, 40, 24), "plain", "inner", "7", "mp", "two-stage"),
+    ((165, 30, 21), "align16", "inner", "7", "pm", "two-stage"),
+    ((65, 21, 20), "plain", "inner", "7", "pm", "two-stage"),         # rows of 64 points, 20 rows
+    ((150, 36, 20), "halo2", "dup", "7", "mp", "two-stage"),
+    ((128, 40, 38), "align2", "odd", "7", "pm", "two-stage"),
+    ((64, 20, 19), "plain", "inner", "7", "mp", "small"),            # rows of 63 points, 19 rows
+    ((40, 20, 20), "align2", "odd", "7", "perm_a", "small"),         # the small-level kernels take any entry order
+    ((50, 21, 13), "halo2", "dup", "7", "perm_b", "small"),
+    ((130, 40, 24), "plain", "inner", "7", "perm_a", "fallback"),    # permuted order on long rows: copy + loops
+    ((70, 20, 12), "plain", "inner", "27", "perm", "fallback"),
+]
+SWEEP_IDS = ["%s-%s-%s-%s" % (c[5], c[1], c[2], c[4]) for c in SWEEP_CASES]
+SWEEP_KINDS = ["rbgs", "rbgs_zero", "rbgs_prolong", "rbgs_boxes", "jacobi2", "jacobi2_prolong", "jacobi2_boxes"]
+
+
+def _boxes2(b, e, nd):
+    """Box 2 of the two-box forms: box 1 shrunk by one point at a lower x and an upper z face (interior faces)."""
+    b2, e2 = list(b), list(e)
+    b2[0] += 1
+    if nd == 3:
+        e2[2] -= 1
+    return b2, e2
+
+
+def _sweep_run(ops, data, kind, lu, lf, lc, st, w, b, e, first, ref):
+    """The entry point (ref False) or its loops (ref True: stencil_cases compositions on the oracle / exact layer)."""
+    u, f, out, uc = fields(ops, data, (lu, lf, lu, lc), 400)
+    L, F, Lc = lu.c_struct(), lf.c_struct(), lc.c_struct()
+    b2, e2 = _boxes2(b, e, lu.nd)
+    tmp = None if ref else ops.new_array(lu.size)
+    if ref:
+        {"rbgs_zero": lambda: S.rbgs_sweep_zero(ops, L, out, F, f, st, w, first, b, e),
+         "rbgs": lambda: S.rbgs_sweep(ops, L, u, out, F, f, st, w, first, b, e),
+         "rbgs_prolong": lambda: S.rbgs_sweep_prolong(ops, L, u, out, F, f, st, w, first, b, e, Lc, uc),
+         "rbgs_boxes": lambda: S.rbgs_sweep_boxes(ops, L, u, out, F, f, st, w, first, b, e, b2, e2),
+         "jacobi2": lambda: S.jacobi2(ops, L, u, out, F, f, st, w, b, e),
+         "jacobi2_prolong": lambda: S.jacobi2_prolong(ops, L, u, out, F, f, st, w, b, e, Lc, uc),
+         "jacobi2_boxes": lambda: S.jacobi2_boxes(ops, L, u, out, F, f, st, w, b, e, b2, e2)}[kind]()
+    else:
+        {"rbgs_zero": lambda: ops.rbgs_sweep_fused_zero(L, out, F, f, st, w, first, b, e),
+         "rbgs": lambda: ops.rbgs_sweep_fused(L, u, out, F, f, st, w, first, b, e),
+         "rbgs_prolong": lambda: ops.rbgs_sweep_fused_prolong(L, u, out, F, f, st, w, first, b, e, Lc, uc),
+         "rbgs_boxes": lambda: ops.rbgs_sweep_fused_boxes(L, u, out, tmp, F, f, st, w, first, b, e, b2, e2),
+         "jacobi2": lambda: ops.jacobi2(L, u, out, tmp, F, f, st, w, b, e),
+         "jacobi2_prolong": lambda: ops.jacobi2_prolong(L, u, out, tmp, F, f, st, w, b, e, Lc, uc),
+         "jacobi2_boxes": lambda: ops.jacobi2_boxes(L, u, out, tmp, F, f, st, w, b, e, b2, e2)}[kind]()
+    return [out, u, f, uc]
+
+
+def _expected_outside(kind, path, want, lu, b, e, st):
+    """include/examg.h: the one-pass kernels write the box only; the fallbacks of the sweep forms (not of the two-box forms and of
+    examg_jacobi2) bring u_in's values (zeros for the zero-field form) to the box's one-stencil-reach shell."""
+    if path != "fallback" or kind in ("rbgs_boxes", "jacobi2_boxes", "jacobi2"):
+        return want[0]
+    src = np.zeros_like(want[1]) if kind == "rbgs_zero" else want[1]
+    return with_shell(want[0], src, lu, b, e, reach(st))
+
+
+def _sweep_case(gpu, orc, ex, case, kind, data, first=0):
+    shape, lay, which, skind, order, path = case
+    nd = 3
+    lu, lf = layouts(nd, shape, lay)
+    lc = FieldLayout.node(3, tuple(s // 2 for s in shape), lu.ghost[0], True, True, ALIGN[lay])
+    b, e = box(nd, shape, which)
+    if kind.endswith("prolong") and which == "dup":
+        b = [1, 1, 1]                # the correction loop's box starts at a non-negative fine index
+    st = stencil(skind, order, data, shape)
+    w = weight(st, data)
+    b2, e2 = _boxes2(b, e, nd)
+    two = kind.endswith("_boxes")
+    elig = gpu.two_stage_eligible(lu.c_struct(), lf.c_struct(), st, b, e, *((b2, e2) if two else (b, e)))
+    if two and (path == "small" or (path == "two-stage" and e2[0] - b2[0] < 64)):
+        assert not elig                      # the small-level kernels take one box only, the two-stage kernel rows of 64 points
+        path = "fallback"
+    else:
+        assert elig == (path != "fallback"), "%s: the case was meant for the %s path" % (kind, path)
+    R = ref_ops(data, orc, ex)
+    got = host(gpu, _sweep_run(gpu, data, kind, lu, lf, lc, st, w, b, e, first, False))
+    want = host(R, _sweep_run(R, data, kind, lu, lf, lc, st, w, b, e, first, True))
+    want[0] = _expected_outside(kind, path, want, lu, b, e, st)
+    assert_same(got, want, "%s %s %s" % (kind, path, order))
+
+
+@pytest.mark.parametrize("data", DATA)
+@pytest.mark.parametrize("case,kind", [(c, k) for c in SWEEP_CASES for k in SWEEP_KINDS if not (c[3] == "27" and "rbgs" in k)],
+                         ids=["%s-%s" % (i, k) for c, i in zip(SWEEP_CASES, SWEEP_IDS) for k in SWEEP_KINDS if not (c[3] == "27" and "rbgs" in k)])
+def test_one_pass_sweeps(hip, orc, ex, case, kind, data):
+    """examg_rbgs_sweep_fused / _zero / _prolong / _boxes and examg_jacobi2 / _prolong / _boxes on the product library: the two-stage
+    kernel, the small-level kernels (rows shorter than 64 points) and the fallback, the path asserted through
+    examg_two_stage_eligible; u_out over the whole array, the inputs unchanged."""
+    _sweep_case(hip, orc, ex, case, kind, data, first=1 if "rbgs" in kind and case[1] == "align16" else 0)
+
+
+@pytest.mark.parametrize("data", DATA)
+@pytest.mark.parametrize("kind", ["rbgs", "jacobi2", "rbgs_prolong", "jacobi2_boxes"])
+def test_two_stage_workgroup_shapes(orc, ex, two_stage_variant, kind, data):
+    """The two-stage kernel in every workgroup shape (product choice, 5 / 8 waves of two rows, 8 waves of three) on an asymmetric
+    stencil in both canonical orders."""
+    for case in (((165, 30, 21), "plain", "inner", "7", "pm", "two-stage"), ((130, 40, 24), "align2", "odd", "7", "mp", "two-stage")):
+        _sweep_case(two_stage_variant, orc, ex, case, kind, data, first=1)
+
+
+# -- three steps in one pass ----------------------------------------------------------------------------------------------------------
+def _three_run(ops, data, kind, lu, lf, st, w, b, e, ref, seed=500):
+    u, f, out = fields(ops, data, (lu, lf, lu), seed)
+    L, F = lu.c_struct(), lf.c_struct()
+    first = 1 if kind == "colours3_1" else 0
+    if kind == "jacobi3":
+        if ref:
+            S.jacobi3(ops, L, u, out, F, f, st, w, b, e)
+        else:
+            ops.jacobi3(L, u, out, ops.new_array(lu.size), F, f, st, w, b, e)
+    elif ref:
+        S.rbgs_colours3(ops, L, u, out, F, f, st, w, first, b, e)
+    else:
+        ops.rbgs_colours3(L, u, out, F, f, st, w, first, b, e)
+    return [out, u, f]
+
+
+def _three_case(gpu, orc, ex, shape, lay, which, order, kind, data, eligible, skind="7"):
+    lu, lf = layouts(3, shape, lay)
+    b, e = box(3, shape, which)
+    st = stencil(skind, order, data, shape)
+    w = weight(st, data)
+    assert gpu.three_stage_eligible(lu.c_struct(), lf.c_struct(), st, b, e) == eligible
+    R = ref_ops(data, orc, ex)
+    got = host(gpu, _three_run(gpu, data, kind, lu, lf, st, w, b, e, False))
+    want = host(R, _three_run(R, data, kind, lu, lf, st, w, b, e, True))
+    pair = gpu.two_stage_eligible(lu.c_struct(), lf.c_struct(), st, b, e, b, e)
+    if not eligible and (kind != "jacobi3" or not pair):     # include/examg.h: examg_jacobi3 / examg_rbgs_colours3
+        want[0] = with_shell(want[0], want[1], lu, b, e, reach(st))
+    assert_same(got, want, "%s %s %s" % (kind, order, "one pass" if eligible else "fallback"))
+
+
+THREE_CASES = [
+    ((136, 120, 70), "plain", "inner", "mp", True),
+    ((140, 124, 74), "align16", "odd", "pm", True),
+    ((150, 130, 60), "halo2", "dup", "pm", True),
+    ((140, 20, 420), "align2", "inner", "mp", False),      # 19 rows: below the bound of 20
+    ((140, 21, 420), "plain", "inner", "pm", True),        # 20 rows
+    ((136, 120, 70), "plain", "inner", "perm_b", False),   # permuted order: the loops one after the other
+    ((64, 130, 130), "plain", "inner", "mp", False),       # rows of 63 points
+]
+
+
+@pytest.mark.parametrize("data", DATA)
+@pytest.mark.parametrize("kind", ["jacobi3", "colours3_0", "colours3_1"])
+@pytest.mark.parametrize("shape,lay,which,order,eligible", THREE_CASES, ids=["%s-%s-%s-%s" % (c[0][0], c[1], c[2], c[3]) for c in THREE_CASES])
+def test_three_steps_in_one_pass(hip3, orc, ex, shape, lay, which, order, eligible, kind, data):
+    """examg_jacobi3 / examg_rbgs_colours3 with the size bound lowered to 2^20 points (debug build); the path asserted through
+    examg_three_stage_eligible; outside the box: nothing written by the one-pass kernel, u_in's shell values by the fallback (by
+    examg_jacobi3's only where its step pair cannot run in one pass)."""
+    _three_case(hip3, orc, ex, shape, lay, which, order, kind, data, eligible)
+
+
+@pytest.mark.parametrize("data", DATA)
+def test_three_steps_forced_chunk_lengths(hipd, orc, ex, data):
+    """The three-step pass with forced z chunks of 5, 33 and 200 planes."""
+    hipd.L.examg_debug_three_stage.argtypes = [C.c_int] * 2
+    try:
+        for zc in (5, 33, 200):
+            hipd.L.examg_debug_three_stage(2, zc)
+            for kind in ("jacobi3", "colours3_1"):
+                _three_case(hipd, orc, ex, (140, 100, 131), "plain", "inner", "pm", kind, data, True)
+    finally:
+        hipd.L.examg_debug_three_stage(0, -1)
+
+
+@pytest.mark.parametrize("kind", ["jacobi3", "colours3_0"])
+def test_three_steps_on_the_product_library(hip, orc, ex, kind):
+    """The product's own bound (8e6 points): 264 x 200 x 170, random data against the oracle, exact data against the reference."""
+    for data, order in (("random", "pm"), ("exact", "mp")):
+        _three_case(hip, orc, ex, (264, 200, 170), "plain", "inner", order, kind, data, True)
+
+
+# -- Jacobi step + residual ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("data", DATA)
+@pytest.mark.parametrize("shape,lay,which,order", [((130, 40, 24), "plain", "inner", "mp"), ((96, 30, 12), "align16", "odd", "pm"),
+                                                   ((64, 20, 14), "halo2", "dup", "perm_a"), ((70, 20, 12), "plain", "inner", "27")])
+def test_jacobi_residual(hip, orc, ex, shape, lay, which, order, data):
+    """examg_jacobi_residual: u_out = J(u_in) and res = rhs - A u_out on the box, u_out holding u_in's values on the shell."""
+    lu, lf = layouts(3, shape, lay)
+    b, e = box(3, shape, which)
+    st = stencil("27", "perm", data, shape) if order == "27" else stencil("7", order, data, shape)
+    w = weight(st, data)
+
+    def run(ops, ref):
+        u, f, res = fields(ops, data, (lu, lf, lu), 600)
+        out = ops.clone(u) if hasattr(ops, "clone") else u.clone()
+        L, F = lu.c_struct(), lf.c_struct()
+        if ref:
+            S.jacobi_residual(ops, L, u, out, F, f, L, res, st, w, b, e)
+        else:
+            ops.jacobi_residual(L, u, out, F, f, L, res, st, w, b, e)
+        return [out, res, u, f]
+
+    R = ref_ops(data, orc, ex)
+    assert_same(host(hip, run(hip, False)), host(R, run(R, True)), "jacobi_residual %s" % order)
+
+
+# -- residual + restriction ------------------------------------------------------------------------------------------------------------
+RR_CASES = [
+    # (cells, layout, order, scale, one pass?)
+    ((134, 70, 40), "plain", "mp", 1.0, True),          # the wide kernel, narrow windows for the left-over columns
+    ((200, 72, 44), "align16", "pm", 4.0, True),
+    ((130, 66, 36), "halo2", "pm", 1.0, True),
+    ((64, 40, 40), "plain", "mp", 4.0, True),           # coarse rows of 31 points: the small one-pass kernel
+    ((40, 20, 20), "align2", "perm_a", 1.0, True),      # the small kernel, a permuted order
+    ((134, 70, 40), "plain", "perm_b", 1.0, False),     # permuted order on long rows: residual loop + restriction
+]
+
+
+def _rr_run(ops, data, lu, lf, lc, st, scale, fb, fe, cb, ce, ref):
+    u, f, fc = fields(ops, data, (lu, lf, lc), 700)
+    if ref:
+        S.residual_restrict(ops, lu.c_struct(), u, lf.c_struct(), f, st, lc.c_struct(), fc, scale, fb, fe, cb, ce)
+    else:
+        r = ops.new_array(lu.size)
+        ops.residual_restrict(lu.c_struct(), u, lf.c_struct(), f, lu.c_struct(), r, st, lc.c_struct(), fc, scale, fb, fe, cb, ce)
+    return [fc, u, f]
+
+
+def _rr_geometry(shape, lay):
+    lu, lf = layouts(3, shape, lay)
+    cs = tuple(s // 2 for s in shape)
+    lc = FieldLayout.node(3, cs, 0, True, False, ALIGN[lay])
+    return lu, lf, lc, [1, 1, 1], list(shape), [1, 1, 1], list(cs)
+
+
+@pytest.mark.parametrize("data", DATA)
+@pytest.mark.parametrize("shape,lay,order,scale,one_pass", RR_CASES, ids=["%s-%s-%s" % (c[0][0], c[1], c[2]) for c in RR_CASES])
+def test_residual_restrict(hip, orc, ex, shape, lay, order, scale, one_pass, data):
+    """examg_residual_restrict on its three paths (wide one-pass, small one-pass, residual + restriction), asserted through
+    examg_residual_restrict_one_pass; the whole coarse array (outside the restriction's box it keeps what it held)."""
+    lu, lf, lc, fb, fe, cb, ce = _rr_geometry(shape, lay)
+    st = stencil("7", order, data, shape)
+    assert hip.residual_restrict_one_pass(lu.c_struct(), lf.c_struct(), st, lc.c_struct(), fb, fe, cb, ce) == one_pass
+    R = ref_ops(data, orc, ex)
+    assert_same(host(hip, _rr_run(hip, data, lu, lf, lc, st, scale, fb, fe, cb, ce, False)),
+                host(R, _rr_run(R, data, lu, lf, lc, st, scale, fb, fe, cb, ce, True)), "residual_restrict %s" % order)
+
+
+@pytest.mark.parametrize("data", DATA)
+def test_residual_restrict_forced_narrow_windows(hipd, orc, ex, data):
+    """k_residual_restrict3 with one and two coarse rows per wave and every tile order (debug build)."""
+    L = hipd.L
+    L.examg_debug_residual_restrict.argtypes = [C.c_int] * 2
+    L.examg_debug_rr_order.argtypes = [C.c_int]
+    shape = (182, 44, 20)
+    lu, lf, lc, fb, fe, cb, ce = _rr_geometry(shape, "plain")
+    st = stencil("7", "pm", data, shape)
+    R = ref_ops(data, orc, ex)
+    want = host(R, _rr_run(R, data, lu, lf, lc, st, 4.0, fb, fe, cb, ce, True))
+    try:
+        for rows in (1, 2):
+            L.examg_debug_residual_restrict(0, (1000 if rows == 2 else 2000) + 8)
+            for order in (0, 2, 1):
+                L.examg_debug_rr_order(order)
+                got = host(hipd, _rr_run(hipd, data, lu, lf, lc, st, 4.0, fb, fe, cb, ce, False))
+                assert_same(got, want, "residual_restrict, %d rows per wave, order %d" % (rows, order))
+    finally:
+        L.examg_debug_rr_order(0)
+        L.examg_debug_residual_restrict(0, 8)
+
+
+# -- residual norm ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape,lay,order", [((130, 40, 24), "plain", "mp"), ((200, 72, 44), "align16", "pm"), ((96, 30, 12), "halo2", "perm_a"),
+                                             ((40, 20, 20), "plain", "pm")])
+def test_residual_norm2(hip, orc, ex, shape, lay, order):
+    """examg_residual_norm2 (one pass for the canonical orders on long rows, residual + dot otherwise): integer coefficients and
+    data give integer residuals, whose squares sum exactly in any order -- equality with the exact value; random data: 1e-13
+    relative against the oracle's two loops."""
+    lu, lf = layouts(3, shape, lay)
+    b, e = [1, 1, 1], [shape[0], shape[1] - 1, shape[2]]
+    for data in DATA:
+        st = stencil("int7", order, data, shape)
+
+        def run(ops):
+            u, f, r = fields(ops, data, (lu, lf, lu), 800)
+            s = ops.residual_norm2(lu.c_struct(), u, lf.c_struct(), f, st, b, e, lu.c_struct(), r)
+            return s if isinstance(s, float) else ops.scalar_value(s)
+
+        got = run(hip)
+        want = run(ex if data == "exact" else orc)
+        if data == "exact":
+            assert got == want and want > 0, (got, want)
+        else:
+            assert abs(got - want) <= 1e-13 * want, (got, want)
+
+
+# -- the interpreter on an asymmetric program -------------------------------------------------------------------------------------------
+def test_convection_diffusion_program_on_gpu(hip):
+    """The convection-diffusion V-cycle of test_stencil_exact.py on the MI355X: printed residuals against the oracle to rounding (the
+    norms' reduction trees differ), fused against unfused bit for bit, the fusions and the one-pass sweeps taken."""
+    from test_gpu_exa4 import _close
+    from test_stencil_exact import convdiff_program
+
+    P = convdiff_program(hip)
+    P.run()
+    O = convdiff_program(OracleOps())
+    O.run()
+    _close(P.printed_values, O.printed_values, O.printed_values[0])
+    Q = convdiff_program(hip, fuse=False)
+    Q.run()
+    assert P.printed_values == Q.printed_values
+    assert P.fusions["residual_restrict"] > 0 and P.fusions["folded_correction"] > 0 and P.fusions["zero_start"] > 0
+    assert P.launches < Q.launches
+    assert np.array_equal(hip.to_host(P.fields[("u", 6)].data()), hip.to_host(Q.fields[("u", 6)].data()))

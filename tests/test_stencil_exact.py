@@ -1,0 +1,366 @@
+"""The CPU oracle (oracle/examg_oracle.c) against the exact reference of tests/stencil_cases.py, on asymmetric constant stencils in
+several entry orders and on exact data: every loop and every composition that the GPU parity tests use as their yardstick must
+return exactly the mathematical value.  No GPU needed."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import stencil_cases as S
+from oracle_ops import OracleOps
+from stencil_cases import APPLY, RESIDUAL, SMOOTH, ExactOps
+
+from exastencils_amd.layout import FieldLayout
+
+
+@pytest.fixture(scope="module")
+def orc():
+    return OracleOps()
+
+
+@pytest.fixture(scope="module")
+def ex():
+    return ExactOps()
+
+
+def _stencil(kind, order):
+    return {"7": S.exact7, "5": S.exact5, "27": S.exact27}[kind](order)
+
+
+KINDS = [("7", o) for o in S.ORDERS7] + [("5", o) for o in S.ORDERS5] + [("27", o) for o in S.ORDERS27]
+
+
+def _geometry(kind, variant):
+    """(nd, cells, u layout, rhs layout, box): a non-cube fragment; `variant`: plain, padded (align 2 / 16), two ghost layers, a
+    box over the duplicate planes, a box inside the inner points with odd origins."""
+    nd = 2 if kind == "5" else 3
+    shape = (13, 10, 8) if nd == 3 else (17, 12, 0)
+    ghost, align = 1, 0
+    if variant == "align2":
+        align = 2
+    elif variant == "align16":
+        align = 16
+    elif variant == "ghost2":
+        ghost = 2
+    lu = FieldLayout.node(nd, shape, ghost, align=align)
+    lf = FieldLayout.node(nd, shape, 1 if variant == "ghost2" else 0, align=align)
+    if variant == "dup":
+        b, e = [0, 0, 0], [shape[0] + 1, shape[1] + 1, shape[2] + 1 if nd == 3 else 1]
+    elif variant == "inside":
+        b, e = [3, 1, 3 if nd == 3 else 0], [shape[0] - 2, shape[1] - 1, shape[2] - 1 if nd == 3 else 1]
+    else:
+        b, e = [1, 1, 1 if nd == 3 else 0], [shape[0], shape[1], shape[2] if nd == 3 else 1]
+    return nd, shape, lu, lf, b, e
+
+
+def _fields(ops, lays, seed):
+    return [ops.from_host(S.int_field(l.size, seed + i)) for i, l in enumerate(lays)]
+
+
+def _host(ops, ts):
+    return [np.array(ops.to_host(t), dtype=np.float64, copy=True) for t in ts]
+
+
+def _assert_equal(got, want, what):
+    for i, (g, w) in enumerate(zip(got, want)):
+        if not np.array_equal(g, w):
+            d = np.abs(g - w)
+            raise AssertionError("%s[%d]: %d of %d values differ, max abs %.3e" % (what, i, int((d > 0).sum()), d.size, d.max()))
+
+
+def test_the_stencils_are_asymmetric():
+    """Mirror coefficients differ in every stencil kind, also in magnitude for the stars; the weights are not 0.8 / diag."""
+    for st in [S.exact7(), S.exact5(), S.convdiff7((130, 120, 110)), S.convdiff5((257, 200, 0)), S.exact7(coefs=S.INT7)]:
+        c = dict(zip(st.offsets, st.coefs))
+        for d in range(3 if len(c) == 7 else 2):
+            m = [0, 0, 0]
+            m[d] = 1
+            assert abs(c[tuple(m)]) != abs(c[tuple(-v for v in m)])
+        assert len(set(abs(v) for v in c.values())) == len(c)
+    for st in (S.exact27(), S.random27()):
+        c = dict(zip(st.offsets, st.coefs))
+        assert all(c[o] != c[tuple(-v for v in o)] for o in c if o != (0, 0, 0))
+    assert S.EXACT_W != 0.8 / S.exact7().diag and S.free_weight(S.convdiff7((64, 64, 64))) != 0.8 / S.convdiff7((64, 64, 64)).diag
+    for k, o in KINDS:
+        st = _stencil(k, o)
+        if o.startswith("perm"):
+            assert st.offsets[0] != (0, 0, 0)
+
+
+def test_exact_reference_refuses_what_it_cannot_do_exactly(ex):
+    """Non-dyadic coefficients and in-place colour loops of a 27-point stencil (loop-order dependent) are refused, not rounded."""
+    lu = FieldLayout.node(3, (6, 6, 6), 1)
+    u, f = ex.from_host(S.int_field(lu.size, 1)), ex.from_host(S.int_field(lu.size, 2))
+    with pytest.raises(ValueError):
+        ex.stencil_op(SMOOTH, lu, u, lu, f, lu, ex.clone(u), S.convdiff7((6, 6, 6)), 0.1, -1, [1, 1, 1], [6, 6, 6])
+    with pytest.raises(ValueError):
+        ex.stencil_op(SMOOTH, lu, u, lu, f, lu, u, S.exact27(), S.EXACT_W, 0, [1, 1, 1], [6, 6, 6])
+    with pytest.raises(AssertionError):      # values out of the exactly representable range
+        big = ex.from_host(np.full(lu.size, 2.0 ** 19))
+        ex.stencil_op(APPLY, lu, big, None, None, lu, ex.clone(u), S.exact27(), 0.0, -1, [1, 1, 1], [6, 6, 6])
+
+
+@pytest.mark.parametrize("kind,order", KINDS)
+@pytest.mark.parametrize("variant", ["plain", "align2", "align16", "ghost2", "dup", "inside"])
+def test_oracle_stencil_loop_is_exact(orc, ex, kind, order, variant):
+    """orc_stencil_op in APPLY, RESIDUAL and SMOOTH, colour -1, 0 and 1, over the whole destination array (outside the box it keeps
+    what it held).  The 27-point stencil's colour loops run out of place: in place they depend on the loop order."""
+    st = _stencil(kind, order)
+    nd, shape, lu, lf, b, e = _geometry(kind, variant)
+    for mode in (APPLY, RESIDUAL, SMOOTH):
+        for colour in ((-1, 0, 1) if mode == SMOOTH else (-1,)):
+            in_place = colour >= 0 and kind != "27"
+
+            def run(ops):
+                u, f, d = _fields(ops, (lu, lf, lu), 10)
+                dst = u if in_place else d
+                ops.stencil_op(mode, lu.c_struct(), u, lf.c_struct(), f, lu.c_struct(), dst, st, S.EXACT_W, colour, b, e)
+                return _host(ops, (u, f, d))
+
+            _assert_equal(run(orc), run(ex), "%s-point %s, %s, mode %d colour %d" % (kind, order, variant, mode, colour))
+
+
+@pytest.mark.parametrize("nd,shape,scale,box", [
+    (3, (14, 10, 12), 1.0, "inner"), (3, (14, 10, 12), 4.0, "dup"), (3, (18, 12, 10), 4.0, "inside"), (2, (18, 14, 0), 1.0, "inner"),
+    (2, (18, 14, 0), 4.0, "dup")])
+@pytest.mark.parametrize("align", [0, 2])
+def test_oracle_transfers_are_exact(orc, ex, nd, shape, scale, box, align):
+    """orc_restrict (full weighting, scale 1 and 4) and orc_prolong_add (trilinear interpolation added), whole arrays."""
+    cs = tuple(s // 2 for s in shape)
+    lfi, lco, lrh = FieldLayout.node(nd, shape, 1, align=align), FieldLayout.node(nd, cs, 1, align=align), FieldLayout.node(nd, cs, 0, align=align)
+    z = 1 if nd == 3 else 0
+    if box == "inner":
+        cb, ce, fb, fe = [1, 1, z], [cs[0], cs[1], cs[2] if nd == 3 else 1], [1, 1, z], [shape[0], shape[1], shape[2] if nd == 3 else 1]
+    elif box == "dup":
+        cb, ce, fb, fe = [0, 1, 0], [cs[0] + 1, cs[1], cs[2] + 1 if nd == 3 else 1], [0, 0, 0], [shape[0] + 1, shape[1] + 1, shape[2] + 1 if nd == 3 else 1]
+    else:
+        cb, ce, fb, fe = [2, 1, 3 if nd == 3 else 0], [cs[0] - 1, cs[1] - 2, cs[2] - 1 if nd == 3 else 1], [3, 1, 3 if nd == 3 else 0], [shape[0] - 2, shape[1] - 3, shape[2] - 1 if nd == 3 else 1]
+
+    def run(ops):
+        r, fc, uc, uf = _fields(ops, (lfi, lrh, lco, lfi), 20)
+        ops.restrict(lfi.c_struct(), r, lrh.c_struct(), fc, scale, cb, ce)
+        ops.prolong_add(lco.c_struct(), uc, lfi.c_struct(), uf, fb, fe)
+        return _host(ops, (r, fc, uc, uf))
+
+    _assert_equal(run(orc), run(ex), "transfers")
+
+
+def _comp_geometry(kind):
+    nd = 2 if kind == "5" else 3
+    shape = (14, 12, 10) if nd == 3 else (18, 14, 0)
+    lu, lf = FieldLayout.node(nd, shape, 1), FieldLayout.node(nd, shape, 0)
+    lc = FieldLayout.node(nd, tuple(s // 2 for s in shape), 1)
+    b, e = [1, 1, 1 if nd == 3 else 0], [shape[0], shape[1], shape[2] if nd == 3 else 1]
+    b2, e2 = [2, 1, 2 if nd == 3 else 0], [shape[0] - 1, shape[1], shape[2] - 1 if nd == 3 else 1]
+    return nd, shape, lu, lf, lc, b, e, b2, e2
+
+
+COMPOSITIONS = ["jacobi2", "jacobi3", "rbgs_sweep_fused", "rbgs_sweep_fused_zero", "rbgs_sweep_fused_prolong", "rbgs_sweep_fused_boxes",
+                "rbgs_colours3", "jacobi2_prolong", "jacobi2_boxes", "jacobi_residual", "residual_restrict"]
+
+
+@pytest.mark.parametrize("kind,order,name", [(k, o, n) for k, o in KINDS if k != "27" for n in COMPOSITIONS] +
+                         [("27", "perm", n) for n in COMPOSITIONS if "rbgs" not in n and "colours" not in n])
+def test_oracle_compositions_are_exact(orc, ex, kind, order, name):
+    """The compositions of OracleOps that the GPU parity tests use as their reference, against the exact loops: the box of the
+    output (their writes outside it differ by design), the inputs untouched.  The 27-point stencil only where no colour loop runs in
+    place."""
+    st = _stencil(kind, order)
+    nd, shape, lu, lf, lc, b, e, b2, e2 = _comp_geometry(kind)
+    if nd == 2 and "prolong" in name:
+        lc = FieldLayout.node(2, tuple(s // 2 for s in shape), 1)
+    L, F, Lc = lu.c_struct(), lf.c_struct(), lc.c_struct()
+    w = S.EXACT_W
+    ob, oe = (b2, e2) if name.endswith("_boxes") else (b, e)
+
+    def run(ops, exact):
+        u, f, out, res, uc = _fields(ops, (lu, lf, lu, lu, lc), 30)
+        if name == "residual_restrict":
+            cs = tuple(s // 2 for s in shape)
+            lr = FieldLayout.node(nd, cs, 0)
+            fc = ops.from_host(S.int_field(lr.size, 77))
+            cb, ce = [1, 1, 1 if nd == 3 else 0], [cs[0], cs[1], cs[2] if nd == 3 else 1]
+            if exact:
+                S.residual_restrict(ops, L, u, F, f, st, lr.c_struct(), fc, 4.0, b, e, cb, ce)
+            else:
+                r = ops.new_array(lu.size)
+                ops.residual_restrict(L, u, F, f, L, r, st, lr.c_struct(), fc, 4.0, b, e, cb, ce)
+            return _host(ops, (fc, u, f)), None
+        if name == "jacobi_residual":
+            out = ops.clone(u) if exact else u.clone()       # u_out holds u_in's values on the box's shell
+            if exact:
+                S.jacobi_residual(ops, L, u, out, F, f, L, res, st, w, b, e)
+            else:
+                ops.jacobi_residual(L, u, out, F, f, L, res, st, w, b, e)
+            return _host(ops, (out, res, u, f)), None
+        tmp = None if exact else u.clone()        # OracleOps.jacobi2 reads the box's shell from tmp
+        if exact:
+            call = {"jacobi2": lambda: S.jacobi2(ops, L, u, out, F, f, st, w, b, e),
+                    "jacobi3": lambda: S.jacobi3(ops, L, u, out, F, f, st, w, b, e),
+                    "rbgs_sweep_fused": lambda: S.rbgs_sweep(ops, L, u, out, F, f, st, w, 1, b, e),
+                    "rbgs_sweep_fused_zero": lambda: S.rbgs_sweep_zero(ops, L, out, F, f, st, w, 0, b, e),
+                    "rbgs_sweep_fused_prolong": lambda: S.rbgs_sweep_prolong(ops, L, u, out, F, f, st, w, 1, b, e, Lc, uc),
+                    "rbgs_sweep_fused_boxes": lambda: S.rbgs_sweep_boxes(ops, L, u, out, F, f, st, w, 0, b, e, b2, e2),
+                    "rbgs_colours3": lambda: S.rbgs_colours3(ops, L, u, out, F, f, st, w, 1, b, e),
+                    "jacobi2_prolong": lambda: S.jacobi2_prolong(ops, L, u, out, F, f, st, w, b, e, Lc, uc),
+                    "jacobi2_boxes": lambda: S.jacobi2_boxes(ops, L, u, out, F, f, st, w, b, e, b2, e2)}[name]
+        else:
+            call = {"jacobi2": lambda: ops.jacobi2(L, u, out, tmp, F, f, st, w, b, e),
+                    "jacobi3": lambda: ops.jacobi3(L, u, out, tmp, F, f, st, w, b, e),
+                    "rbgs_sweep_fused": lambda: ops.rbgs_sweep_fused(L, u, out, F, f, st, w, 1, b, e),
+                    "rbgs_sweep_fused_zero": lambda: ops.rbgs_sweep_fused_zero(L, out, F, f, st, w, 0, b, e),
+                    "rbgs_sweep_fused_prolong": lambda: ops.rbgs_sweep_fused_prolong(L, u, out, F, f, st, w, 1, b, e, Lc, uc),
+                    "rbgs_sweep_fused_boxes": lambda: ops.rbgs_sweep_fused_boxes(L, u, out, tmp, F, f, st, w, 0, b, e, b2, e2),
+                    "rbgs_colours3": lambda: ops.rbgs_colours3(L, u, out, F, f, st, w, 1, b, e),
+                    "jacobi2_prolong": lambda: ops.jacobi2_prolong(L, u, out, tmp, F, f, st, w, b, e, Lc, uc),
+                    "jacobi2_boxes": lambda: ops.jacobi2_boxes(L, u, out, tmp, F, f, st, w, b, e, b2, e2)}[name]
+        call()
+        return _host(ops, (out, u, f, uc)), S.box_mask(lu, ob, oe)
+
+    got, m = run(orc, False)
+    want, _ = run(ex, True)
+    if m is not None:
+        got[0], want[0] = got[0][m], want[0][m]
+    _assert_equal(got, want, "%s, %s-point %s" % (name, kind, order))
+
+
+def test_three_steps_stay_exact_on_the_deepest_composition(ex):
+    """The deepest composition of the GPU suite -- three Jacobi steps, the residual of the result and its restriction -- on the
+    largest exact values the fields take: the reference itself asserts that every value stays exactly representable."""
+    shape = (20, 16, 12)
+    lu, lf, lr = FieldLayout.node(3, shape, 1), FieldLayout.node(3, shape, 0), FieldLayout.node(3, tuple(s // 2 for s in shape), 0)
+    for st in (S.exact7("perm_b"), S.exact27("perm")):
+        u = ex.from_host(np.full(lu.size, 16.0) * np.where(np.arange(lu.size) % 2, 1, -1))
+        f = ex.from_host(np.full(lf.size, -16.0))
+        out, fc = ex.clone(u), ex.new_array(lr.size)
+        S.jacobi3(ex, lu, u, out, lf, f, st, S.EXACT_W, [1, 1, 1], list(shape))
+        S.residual_restrict(ex, lu, out, lf, f, st, lr, fc, 4.0, [1, 1, 1], list(shape), [1, 1, 1], [s // 2 for s in shape])
+        assert np.all(np.isfinite(ex.to_host(fc)))
+
+
+# -- one interpreter run with an asymmetric constant stencil ----------------------------------------------------------------------
+CONVDIFF_EXA4 = """
+Domain global< [0.0, 0.0, 0.0] to [1.0, 1.0, 1.0] >
+
+Layout Halo< Real, Node >@all {
+  duplicateLayers = [1, 1, 1] with communication
+  ghostLayers     = [1, 1, 1] with communication
+}
+Layout Plain< Real, Node >@all {
+  duplicateLayers = [1, 1, 1] with communication
+  ghostLayers     = [0, 0, 0]
+}
+
+Field u< global, Halo, 0.0 >@(all but finest)
+Field u< global, Halo, vf_boundaryPosition_x ** 2 - 0.5 * vf_boundaryPosition_y ** 2 - 0.5 * vf_boundaryPosition_z ** 2 >@finest
+Field f< global, Plain, None >@all
+Field r< global, Halo, 0.0 >@all
+
+Stencil A@all {
+  [ 0,  0,  0] =>  2.0 / ( vf_gridWidth_x ** 2 ) + 1.2 / ( vf_gridWidth_y ** 2 ) + 2.8 / ( vf_gridWidth_z ** 2 ) + 3.0 / vf_gridWidth_x + 2.0 / vf_gridWidth_y + 1.0 / vf_gridWidth_z
+  [-1,  0,  0] => -1.0 / ( vf_gridWidth_x ** 2 ) - 3.0 / vf_gridWidth_x
+  [ 1,  0,  0] => -1.0 / ( vf_gridWidth_x ** 2 )
+  [ 0, -1,  0] => -0.6 / ( vf_gridWidth_y ** 2 )
+  [ 0,  1,  0] => -0.6 / ( vf_gridWidth_y ** 2 ) - 2.0 / vf_gridWidth_y
+  [ 0,  0, -1] => -1.4 / ( vf_gridWidth_z ** 2 ) - 1.0 / vf_gridWidth_z
+  [ 0,  0,  1] => -1.4 / ( vf_gridWidth_z ** 2 )
+}
+Stencil R from default restriction on Node with "linear"
+Stencil P from default prolongation on Node with "linear"
+
+Function Defect@all {
+  communicate u
+  loop over r {
+    r = f - A * u
+  }
+  apply bc to r
+}
+
+Function Norm@finest : Real {
+  Var s : Real = 0.0
+  loop over r with reduction ( + : s ) {
+    s += r * r
+  }
+  return sqrt ( s )
+}
+
+Function Sweeps@all {
+  repeat 3 times {
+    color with {
+      ( i0 + i1 + i2 ) % 2,
+      communicate u
+      loop over u {
+        u += 0.8 / diag ( A ) * ( f - A * u )
+      }
+      apply bc to u
+    }
+  }
+}
+
+Function Cycle@(all but coarsest) {
+  Sweeps ( )
+  Defect ( )
+  communicate r
+  loop over f@coarser {
+    f@coarser = R * r
+  }
+  loop over u@coarser {
+    u@coarser = 0.0
+  }
+  apply bc to u@coarser
+  Cycle@coarser ( )
+  communicate u@coarser
+  loop over u {
+    u += P@coarser * u@coarser
+  }
+  apply bc to u
+  Sweeps ( )
+}
+
+Function Cycle@coarsest {
+  repeat 16 times {
+    Sweeps ( )
+  }
+}
+
+Function Application {
+  apply bc to u@finest
+  Defect@finest ( )
+  Var res0 : Real = Norm@finest ( )
+  Var res : Real = res0
+  print ( "initial residual", res0 )
+  Var it : Int = 0
+  repeat until it >= 5 || res <= 1.0E-9 * res0 {
+    it += 1
+    Cycle@finest ( )
+    Defect@finest ( )
+    res = Norm@finest ( )
+    print ( "cycle", it, "residual", res )
+  }
+}
+"""
+
+
+def convdiff_program(ops, fuse=True, lo=2, hi=6):
+    from exastencils_amd import exa4
+
+    return exa4.Exa4Program(CONVDIFF_EXA4, dict(dimensionality=3, minLevel=lo, maxLevel=hi), ops=ops, fuse=fuse)
+
+
+def test_convection_diffusion_program_fused_equals_unfused():
+    """An ExaSlang-4 V-cycle with a mild convection-diffusion stencil (no two coefficients equal; smoother sweeps on the coarsest
+    level, CG needs a symmetric operator) through the interpreter on the oracle: the one-pass forms and the cross-statement fusions
+    change no bit of the printed residuals or the solution, and the residual goes down."""
+    P = convdiff_program(OracleOps())
+    P.run()
+    Q = convdiff_program(OracleOps(), fuse=False)
+    Q.run()
+    assert P.printed_values == Q.printed_values and len(P.printed_values) >= 4
+    assert sum(P.fusions.values()) > 0 and P.launches < Q.launches
+    assert np.array_equal(P.fields[("u", 6)].data().numpy(), Q.fields[("u", 6)].data().numpy())
+    assert P.printed_values[-1] < 0.1 * P.printed_values[0]

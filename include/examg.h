@@ -109,7 +109,11 @@ int examg_device_count(void);
  *   ww = (1.0 / cfield[diag]) * w for stencil fields (w = omega, Testing/SISC/3D_VarCoeff.exa4:145).
  * colour: -1 = all points, else only points with (i0+i1+i2) % 2 == colour
  *   (baseExt/l4/L4_ColorLoops.scala:44-66; condition emitted by IR_LoopOverDimensions.scala:215-216).
- * u and dst may alias only when colour >= 0 (or for disjoint boxes). */
+ * u and dst may alias only when colour >= 0 (or for disjoint boxes).
+ * Every argument is indexed through its own layout: u through lu, rhs through lf, dst through ld and the coefficients of a stencil
+ * field through st->clayout; the four may differ in ghost and pad widths (`cgTmp1 = Laplace * cgTmp0`: no ghost layers / one).  The
+ * diagonal of a stencil field is entry st->diag, wherever it stands in the entry list.  Only the points of the box (of the colour)
+ * are written, in dst alone; u, rhs and the coefficient array are read only -- constant stencils and stencil fields alike. */
 int examg_stencil_op(int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs,
                      const examg_layout_t *ld, double *dst, const examg_stencil_t *st, double w, int colour,
                      const int32_t *begin, const int32_t *end, examg_stream_t stream);
@@ -129,7 +133,10 @@ int examg_residual(const examg_layout_t *lu, const double *u, const examg_layout
  * outside the box at most the one-stencil-reach shell is touched, and only by copying u_in's values there; the
  * caller keeps u_out's duplicate/ghost shell valid the way the program does anyway (`apply bc` / `communicate`
  * after the loop) and swaps the two pointers.  24 B per update instead of 48 B.  3-D 7-point constant stencils
- * take the two-stage kernel (writes the box only); anything else falls back to copy + two half sweeps. */
+ * take the two-stage kernel (writes the box only); anything else -- every stencil field among it -- falls back to copy + two half
+ * sweeps.  What holds for "the fallback" of this and of the following one-pass entry points holds for stencil fields: they have no
+ * one-pass form except the 27-entry record form of examg_jacobi2 / examg_jacobi2_boxes / examg_jacobi_residual, the eligibility
+ * queries answer 0 for them, and outside the box they write what the fallback is said to write. */
 int examg_rbgs_sweep_fused(const examg_layout_t *lu, const double *u_in, double *u_out, const examg_layout_t *lf,
                            const double *rhs, const examg_stencil_t *st, double w, int first, const int32_t *begin,
                            const int32_t *end, examg_stream_t stream);
@@ -343,13 +350,23 @@ int examg_max_err_expr(const examg_layout_t *l, const double *x, const examg_geo
                        const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream);
 
 /* ---- stencil-field initialisation.  Testing/SISC/3D_VarCoeff.exa4:206-217 (2*nd+1 entries): -div(a grad u) with the
- * coefficient expression `a` evaluated half a mesh width to either side of the node. */
+ * coefficient expression `a` evaluated half a mesh width to either side of the node.  With (x, y, z) the node position
+ * (index * h + pos_begin) and, per dimension d, ap_d = a(position + (0.5 * h_d) in d), am_d = a(position - (0.5 * h_d) in d):
+ *   entry 0 (0,0,0)   = ((ap_x + am_x) / (h_x * h_x)) + ((ap_y + am_y) / (h_y * h_y)) [+ ((ap_z + am_z) / (h_z * h_z))]
+ *   entry 1 + 2d (+d) = (-1.0 * ap_d) / (h_d * h_d)
+ *   entry 2 + 2d (-d) = (-1.0 * am_d) / (h_d * h_d)
+ * in the planes layout (EXAMG_CLAYOUT_PLANES) of lc, on the points of [begin,end) only. */
 int examg_init_varcoeff7(const examg_layout_t *lc, double *cfield, const examg_geom_t *g, const examg_expr_t *a,
                          const int32_t *begin, const int32_t *end, examg_stream_t stream);
 
 /* 27-entry stencil field of -div(a grad u) - k^2 u (BASELINE.json config 4): trilinear elements with element-wise
  * constant a = a(element centre) (expression program), lumped mass, scaled by 1/h^3; ksq = k^2.
- * Entry order: (0,0,0), then (dx,dy,dz) lexicographic with dx slowest.  The stencil-field mechanism is the reference's
+ * Entry order: (0,0,0), then the other 26 offsets (dx,dy,dz) with dz slowest and dx fastest: (-1,-1,-1), (0,-1,-1), (1,-1,-1),
+ * (-1,0,-1), ... (1,1,1).  With h = g->h[0] and a_e = a(x +- 0.5 * h, y +- 0.5 * h, z +- 0.5 * h) for the eight elements around the
+ * node, entry (dx,dy,dz) = (S * kf) / (h * h), S = the sum of a_e over the elements that hold both nodes (those on the side of every
+ * non-zero offset component; added with the x side outermost and the z side innermost, the lower side first) and kf = 1.0 / 3.0
+ * for the centre, 0.0 across an edge (one non-zero component), -1.0 / 12.0 across a face or body diagonal; the centre entry then has
+ * ksq subtracted.  Planes layout of lc, the points of [begin,end) only.  The stencil-field mechanism is the reference's
  * (stencil/ir/IR_StencilConvolution.scala:73-95); the reference itself ships 2d+1-entry fields only. */
 int examg_init_helmholtz27(const examg_layout_t *lc, double *cfield, const examg_geom_t *g, const examg_expr_t *a, double ksq,
                            const int32_t *begin, const int32_t *end, examg_stream_t stream);

@@ -331,7 +331,8 @@ enum {
   ORC_FN_KAPPA_COEF2D = 13,
   ORC_FN_POLY2D = 14,
   ORC_FN_SINSINH2D = 15,
-  ORC_FN_XSQ = 16
+  ORC_FN_XSQ = 16,
+  ORC_FN_ASYM3D = 17      /* 1 + x + 2 y^2 + 4 z: +, * and constants only, no mirror or permutation symmetry (tests of the stencil-field initialisation) */
 };
 
 double orc_eval_fn(int fn, const double *p, double x, double y, double z) {
@@ -355,6 +356,7 @@ double orc_eval_fn(int fn, const double *p, double x, double y, double z) {
     case ORC_FN_POLY2D: return (x * x) - (y * y);              /* Testing/BC/2D_Polynomial.exa4:43 */
     case ORC_FN_SINSINH2D: return sin(PI * x) * sinh(PI * y);  /* Testing/BC/2D_Trigonometric.exa4:43 */
     case ORC_FN_XSQ: return x * x;                             /* Testing/BC/2D_Periodic.exa4:43 */
+    case ORC_FN_ASYM3D: return ((1.0 + x) + ((2.0 * y) * y)) + (4.0 * z);
     default: return NAN;
   }
 }

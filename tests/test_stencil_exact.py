@@ -364,3 +364,259 @@ def test_convection_diffusion_program_fused_equals_unfused():
     assert sum(P.fusions.values()) > 0 and P.launches < Q.launches
     assert np.array_equal(P.fields[("u", 6)].data().numpy(), Q.fields[("u", 6)].data().numpy())
     assert P.printed_values[-1] < 0.1 * P.printed_values[0]
+
+
+# -- stencil fields (variable coefficients) -------------------------------------------------------------------------------------------
+from stencil_cases import FoldOps  # noqa: E402
+
+FIELD_KINDS = ["vc7", "vc7_perm_a", "vc7_perm_b", "vc5", "vc5_perm", "h27", "h27_perm"]
+
+
+@pytest.fixture(scope="module")
+def fold():
+    return FoldOps()
+
+
+def _field_geometry(kind, variant):
+    """(nd, u layout, rhs layout, destination layout, coefficient layout, box).  'own': every argument in a layout of its own (ghost
+    widths 2 / 0 / 1 / 1, alignments 0 / 2 / 4 / 16); 'same': destination = u layout and coefficients in the rhs layout object (what
+    the older tests pass); 'dup' / 'inside': own layouts, a box over the duplicate planes / inside the inner points."""
+    nd = 2 if kind.startswith("vc5") else 3
+    shape = (13, 10, 8) if nd == 3 else (17, 12, 0)
+    if variant == "same":
+        lu, lf = FieldLayout.node(nd, shape, 1), FieldLayout.node(nd, shape, 0)
+        ld, lc = lu, lf
+    else:
+        lu, lf = FieldLayout.node(nd, shape, 2), FieldLayout.node(nd, shape, 0, align=2)
+        ld, lc = FieldLayout.node(nd, shape, 1, align=4), FieldLayout.node(nd, shape, 1, align=16)
+    z = nd == 3
+    if variant == "dup":
+        b, e = [0, 0, 0], [shape[0] + 1, shape[1] + 1, shape[2] + 1 if z else 1]
+    elif variant == "inside":
+        b, e = [3, 1, 3 if z else 0], [shape[0] - 2, shape[1] - 1, shape[2] - 1 if z else 1]
+    else:
+        b, e = [1, 1, 1 if z else 0], [shape[0], shape[1], shape[2] if z else 1]
+    return nd, lu, lf, ld, lc, b, e
+
+
+def _field_run(ops, kind, variant, data, mode, colour, wform, in_place):
+    nd, lu, lf, ld, lc, b, e = _field_geometry(kind, variant)
+    st = S.stencil_field(ops, S.field_offsets(kind), lc, data, 41, wform)
+    u, f = S.data_field(ops, lu.size, data, 42), S.data_field(ops, lf.size, data, 43)
+    d = S.data_field(ops, ld.size, data, 44)
+    w = S.EXACT_W if data == "exact" else 0.713
+    if in_place:
+        ops.stencil_op(mode, lu.c_struct(), u, lf.c_struct(), f, lu.c_struct(), u, st, w, colour, b, e)
+    else:
+        ops.stencil_op(mode, lu.c_struct(), u, lf.c_struct(), f, ld.c_struct(), d, st, w, colour, b, e)
+    return _host(ops, (u, f, d, st.cfield))
+
+
+def test_the_stencil_field_data_is_what_the_tests_need(ex):
+    """Entry lists: the reference's order and permutations with the centre elsewhere.  Exact coefficients: multiples of 1/4 of both
+    signs over the whole allocation, no two entries of a point's neighbourhood systematically equal, the diagonal from {4, 8, 16}.
+    The distinct layouts differ in size, reference offset and row length: an index formed with another argument's layout lands on
+    another point."""
+    from exastencils_amd.field import helmholtz27_offsets, stencil_field_offsets
+
+    assert S.field_offsets("vc7") == stencil_field_offsets(3) and S.field_offsets("h27") == helmholtz27_offsets()
+    for kind in FIELD_KINDS:
+        offs = S.field_offsets(kind)
+        nd, lu, lf, ld, lc, b, e = _field_geometry(kind, "own")
+        a = S.coefficient_array(offs, lc, "exact", 41).reshape(len(offs), lc.size)
+        d = offs.index((0, 0, 0))
+        assert (d != 0) == ("perm" in kind)
+        assert set(np.unique(a[d])) == set(S.EXACT_DIAGS)
+        off = np.delete(a, d, axis=0)
+        assert np.array_equal(off * 4, np.round(off * 4)) and (off > 0).any() and (off < 0).any() and not (off == 0).any()
+        assert all(not np.array_equal(a[i], a[j]) for i in range(len(offs)) for j in range(i))
+        r = S.coefficient_array(offs, lc, "random", 41).reshape(len(offs), lc.size)
+        assert (np.delete(r, d, axis=0) < 0).any() and r[d].min() >= 2.0
+        lays = [S._Lay(l) for l in (lu, lf, ld, lc)]
+        assert len({(tuple(L.tot), tuple(L.ref)) for L in lays}) == 4 and len({L.tot[0] for L in lays}) == 4
+
+
+@pytest.mark.parametrize("kind", FIELD_KINDS)
+@pytest.mark.parametrize("variant", ["own", "same", "dup", "inside"])
+def test_oracle_stencil_field_loop_is_exact(orc, ex, kind, variant):
+    """orc_stencil_op on a stencil field, exact data, against the exact reference: APPLY, RESIDUAL and SMOOTH with colours -1, 0, 1 and
+    both weight forms, over the whole u, rhs, destination and coefficient arrays.  The 27-entry fields' colour loops run out of place."""
+    for mode in (APPLY, RESIDUAL, SMOOTH):
+        for colour in ((-1, 0, 1) if mode == SMOOTH else (-1,)):
+            for wform in ((0, 1) if mode == SMOOTH else (0,)):
+                in_place = colour >= 0 and not kind.startswith("h27")
+                got = _field_run(orc, kind, variant, "exact", mode, colour, wform, in_place)
+                want = _field_run(ex, kind, variant, "exact", mode, colour, wform, in_place)
+                _assert_equal(got, want, "%s %s, mode %d colour %d wform %d" % (kind, variant, mode, colour, wform))
+
+
+@pytest.mark.parametrize("kind", FIELD_KINDS)
+@pytest.mark.parametrize("variant", ["own", "same", "dup"])
+def test_oracle_stencil_field_loop_folds_as_the_header_says(orc, fold, kind, variant):
+    """The same on random data against the float64 restatement of the statement order, bit for bit; the two weight forms and a
+    diagonal taken from entry 0 must differ from the right result somewhere (the data can tell them apart)."""
+    for mode in (APPLY, RESIDUAL, SMOOTH):
+        for colour in ((-1, 0, 1) if mode == SMOOTH else (-1,)):
+            for wform in ((0, 1) if mode == SMOOTH else (0,)):
+                in_place = colour >= 0 and not kind.startswith("h27")
+                got = _field_run(orc, kind, variant, "random", mode, colour, wform, in_place)
+                want = _field_run(fold, kind, variant, "random", mode, colour, wform, in_place)
+                _assert_equal(got, want, "%s %s, mode %d colour %d wform %d" % (kind, variant, mode, colour, wform))
+    a = _field_run(fold, kind, variant, "random", SMOOTH, -1, 0, False)
+    b = _field_run(fold, kind, variant, "random", SMOOTH, -1, 1, False)
+    assert not np.array_equal(a[2], b[2])
+
+
+def test_fold_reference_equals_the_oracle_on_constant_stencils(orc, fold):
+    """FoldOps on constant stencils (asymmetric, permuted orders): the bits of the oracle's loop."""
+    for st, nd in ((S.convdiff7((13, 10, 8), "perm_b"), 3), (S.convdiff5((17, 12, 0), "perm_a"), 2), (S.random27("perm"), 3)):
+        shape = (13, 10, 8) if nd == 3 else (17, 12, 0)
+        lu, lf, ld = FieldLayout.node(nd, shape, 2), FieldLayout.node(nd, shape, 0, align=2), FieldLayout.node(nd, shape, 1, align=4)
+        b, e = [1, 1, 1 if nd == 3 else 0], [shape[0], shape[1], shape[2] if nd == 3 else 1]
+        for mode in (APPLY, RESIDUAL, SMOOTH):
+            def run(ops):
+                u, f, d = (S.data_field(ops, l.size, "random", 50 + i) for i, l in enumerate((lu, lf, ld)))
+                ops.stencil_op(mode, lu.c_struct(), u, lf.c_struct(), f, ld.c_struct(), d, st, S.free_weight(st), -1, b, e)
+                return _host(ops, (u, f, d))
+
+            _assert_equal(run(orc), run(fold), "constant stencil, mode %d" % mode)
+
+
+def test_exact_reference_refuses_stencil_fields_it_cannot_do_exactly(ex):
+    """A transformed coefficient array, a diagonal that is no power of two and coefficients finer than 2^-8 are refused."""
+    import dataclasses
+
+    lu, lc = FieldLayout.node(3, (6, 6, 6), 1), FieldLayout.node(3, (6, 6, 6), 0)
+    offs = S.field_offsets("vc7")
+    u, f = ex.from_host(S.int_field(lu.size, 1)), ex.from_host(S.int_field(lc.size, 2))
+    st = S.stencil_field(ex, offs, lc, "exact", 3)
+    args = (lu, u, lc, f, lu, ex.clone(u))
+    ex.stencil_op(SMOOTH, *args, st, S.EXACT_W, -1, [1, 1, 1], [6, 6, 6])
+    with pytest.raises(ValueError):
+        ex.stencil_op(SMOOTH, *args, dataclasses.replace(st, ctransform=1), S.EXACT_W, -1, [1, 1, 1], [6, 6, 6])
+    a = S.coefficient_array(offs, lc, "exact", 3)
+    a[:lc.size] = 6.0
+    with pytest.raises(ValueError):
+        ex.stencil_op(SMOOTH, *args, dataclasses.replace(st, cfield=ex.from_host(a)), S.EXACT_W, -1, [1, 1, 1], [6, 6, 6])
+    a[:lc.size] = 8.0
+    a[lc.size:2 * lc.size] = 2.0 ** -9
+    with pytest.raises(ValueError):
+        ex.stencil_op(APPLY, *args, dataclasses.replace(st, cfield=ex.from_host(a)), 0.0, -1, [1, 1, 1], [6, 6, 6])
+
+
+@pytest.mark.parametrize("kind", ["vc7_perm_b", "h27", "h27_perm"])
+def test_stencil_field_compositions_stay_exact(orc, ex, kind):
+    """The deepest stencil-field compositions of the GPU suite on exact data -- two Jacobi steps and the residual of the result, a
+    Jacobi step + residual, a red-black sweep, the residual of a smoothed field + its restriction -- with distinct layouts: the reference
+    asserts that every value stays exactly representable, and the oracle's loops give the same values.  (Every step of a stencil-field
+    smoother divides by up to 16 * 16: three steps in a row need more than the 32 fractional bits of the reference.)"""
+    shape = (20, 16, 12)
+    lu, lf, lr, lc = (FieldLayout.node(3, shape, 2), FieldLayout.node(3, shape, 0, align=2), FieldLayout.node(3, shape, 1, align=4),
+                      FieldLayout.node(3, shape, 1, align=16))
+    lco = FieldLayout.node(3, tuple(s // 2 for s in shape), 0)
+    b, e = [1, 1, 1], list(shape)
+    cb, ce = [1, 1, 1], [s // 2 for s in shape]
+
+    def run(ops):
+        st = S.stencil_field(ops, S.field_offsets(kind), lc, "exact", 61)
+        u, f, res = (S.data_field(ops, l.size, "exact", 62 + i) for i, l in enumerate((lu, lf, lr)))
+        out, out2, out3 = ops.clone(u) if hasattr(ops, "clone") else u.clone(), S._clone(ops, u), S._clone(ops, u)
+        fc = S.data_field(ops, lco.size, "exact", 66)
+        L, F = lu.c_struct(), lf.c_struct()
+        S.jacobi2(ops, L, u, out, F, f, st, S.EXACT_W, b, e)
+        ops.stencil_op(RESIDUAL, L, out, F, f, lr.c_struct(), res, st, 0.0, -1, b, e)
+        res2 = S._clone(ops, res)
+        S.jacobi_residual(ops, L, u, out2, F, f, lr.c_struct(), res2, st, S.EXACT_W, b, e)
+        if not kind.startswith("h27"):
+            S.rbgs_sweep(ops, L, u, out3, F, f, st, S.EXACT_W, 1, b, e)
+        S.residual_restrict(ops, L, out2, F, f, st, lco.c_struct(), fc, 4.0, b, e, cb, ce)
+        return _host(ops, (out, out2, res, res2, out3, fc, u, f))
+
+    _assert_equal(run(orc), run(ex), "compositions on %s" % kind)
+
+
+def test_residual_norm_of_a_stencil_field_is_exact(orc, ex):
+    """Integer coefficients and integer data: integer residuals, whose squares sum exactly in any order."""
+    shape = (14, 12, 10)
+    lu, lf, lc = FieldLayout.node(3, shape, 2), FieldLayout.node(3, shape, 0, align=2), FieldLayout.node(3, shape, 1, align=16)
+    b, e = [1, 1, 1], list(shape)
+    for kind in ("vc7", "h27_perm"):
+        def run(ops):
+            st = S.stencil_field(ops, S.field_offsets(kind), lc, "exact", 71, unit=1.0)
+            u, f = S.data_field(ops, lu.size, "exact", 72), S.data_field(ops, lf.size, "exact", 73)
+            s = ops.residual_norm2(lu.c_struct(), u, lf.c_struct(), f, st, b, e)
+            return s if isinstance(s, float) else ops.scalar_value(s)
+
+        assert run(orc) == run(ex) > 0
+
+
+# -- stencil-field initialisation --------------------------------------------------------------------------------------------------------
+ORC_FN_ASYM3D = 17      # oracle/examg_oracle.c: ((1.0 + x) + ((2.0 * y) * y)) + (4.0 * z)
+
+
+def _init_geometry(nd):
+    """A coefficient layout with ghost layers and padding, a box off the array edges, a power-of-two mesh width (h * h, 0.5 * h and the
+    positions are exact: the only roundings are those of the coefficient expressions) and a fragment that does not start at 0."""
+    from exastencils_amd.lib import GeomC
+
+    shape = (16, 12, 10) if nd == 3 else (16, 12, 0)
+    lc = FieldLayout.node(nd, shape, 1, align=4)
+    g = GeomC()
+    for d in range(3):
+        g.pos_begin[d] = (0.25, -0.5, 1.0)[d] if d < nd else 0.0
+        g.h[d] = (1.0 / 16, 1.0 / 8, 1.0 / 32)[d] if d < nd else 0.0
+    b, e = [1, 0, 2 if nd == 3 else 0], [shape[0] - 1, shape[1] + 1, shape[2] - 1 if nd == 3 else 1]
+    return lc, g, b, e
+
+
+def test_the_asymmetric_coefficient_separates_mirrorings_and_axis_permutations():
+    """The 48 images of a point under the mirrorings about the centre of the unit cube and the permutations of the axes get 48
+    different coefficients (the exp profile of the reference's program gets one)."""
+    import itertools
+
+    p = np.array([0.1234, 0.2718, 0.4142])          # offsets from the centre
+    vals = set()
+    for perm in itertools.permutations(range(3)):
+        for sg in itertools.product((1, -1), repeat=3):
+            vals.add(float(S.asym_coefficient(*[0.5 + sg[d] * p[perm[d]] for d in range(3)])))
+    assert len(vals) == 48
+    x, y, z = np.array([0.375]), np.array([-0.25]), np.array([1.125])
+    assert OracleOps._eval_program(S.ASYM_PROGRAM, x, y, z)[0] == S.asym_coefficient(x, y, z)[0]
+
+
+@pytest.mark.parametrize("nd", [3, 2])
+def test_oracle_init_varcoeff7_equals_the_definition(orc, nd):
+    """orc_init_varcoeff7 with the asymmetric +, * coefficient against the numpy restatement of include/examg.h, with equality, over
+    the whole array (nothing outside the box is written)."""
+    lc, g, b, e = _init_geometry(nd)
+    K = 2 * nd + 1
+    start = np.random.default_rng(5).uniform(-1.0, 1.0, K * lc.size)
+    cf = orc.from_host(start.copy())
+    orc.init_varcoeff7(lc.c_struct(), cf, g, ORC_FN_ASYM3D, (), b, e)
+    want = start.copy()
+    S.init_varcoeff7_ref(lc, want, g, S.asym_coefficient, b, e)
+    assert np.array_equal(orc.to_host(cf), want)
+    assert int((want != start).sum()) == K * int(np.prod([e[d] - b[d] for d in range(3)]))
+
+
+def test_oracle_init_helmholtz27_equals_the_definition(orc):
+    lc, g, b, e = _init_geometry(3)
+    for d in range(3):
+        g.h[d] = 1.0 / 16
+    start = np.random.default_rng(6).uniform(-1.0, 1.0, 27 * lc.size)
+    cf = orc.from_host(start.copy())
+    orc.init_helmholtz27(lc.c_struct(), cf, g, ORC_FN_ASYM3D, (0.0, 2.5), b, e)
+    want = start.copy()
+    S.init_helmholtz27_ref(lc, want, g, S.asym_coefficient, 2.5, b, e)
+    assert np.array_equal(orc.to_host(cf), want)
+    # the entries of the plane dz = -1 differ from those of dz = +1, and likewise in x and y: the coefficient is not symmetric
+    W = want.reshape(27, -1)
+    from exastencils_amd.field import helmholtz27_offsets
+
+    offs = helmholtz27_offsets()
+    m = S.box_mask(lc, b, e)
+    for o in ((1, 1, 0), (0, 1, 1), (1, 0, 1)):
+        for d in range(3):
+            if o[d]:
+                mir = tuple(-v if i == d else v for i, v in enumerate(o))
+                assert not np.array_equal(W[offs.index(o)][m], W[offs.index(mir)][m])

@@ -241,8 +241,9 @@ extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const exa
 extern "C" int examg_restrict_cell(const examg_layout_t *lf_, const double *rf, const examg_layout_t *lc_, double *fc, double scale,
                                    const int32_t *begin, const int32_t *end, examg_stream_t stream) {
   if (!lf_ || !rf || !lc_ || !fc || !begin || !end) { set_error("examg_restrict_cell: null argument"); return 1; }
+  // the dimensionality first: cell_layout_ok walks the nd dimensions of the per-dimension arrays, and nd = 4 would run as 2-D
+  if (lf_->nd != lc_->nd || (lf_->nd != 2 && lf_->nd != 3)) { set_error("examg_restrict_cell: 2-D or 3-D layouts of one dimensionality"); return 1; }
   if (!cell_layout_ok("examg_restrict_cell", lf_) || !cell_layout_ok("examg_restrict_cell", lc_)) return 1;
-  if (lf_->nd != lc_->nd || lf_->nd < 2) { set_error("examg_restrict_cell: 2-D or 3-D layouts of one dimensionality"); return 1; }
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   const int nd = lf_->nd;
@@ -272,8 +273,9 @@ extern "C" int examg_restrict_cell(const examg_layout_t *lf_, const double *rf, 
 extern "C" int examg_prolong_add_cell(const examg_layout_t *lc_, const double *uc, const examg_layout_t *lf_, double *uf,
                                       const int32_t *begin, const int32_t *end, examg_stream_t stream) {
   if (!lc_ || !uc || !lf_ || !uf || !begin || !end) { set_error("examg_prolong_add_cell: null argument"); return 1; }
+  // the dimensionality first: cell_layout_ok walks the nd dimensions of the per-dimension arrays, and nd = 4 would run as 2-D
+  if (lf_->nd != lc_->nd || (lf_->nd != 2 && lf_->nd != 3)) { set_error("examg_prolong_add_cell: 2-D or 3-D layouts of one dimensionality"); return 1; }
   if (!cell_layout_ok("examg_prolong_add_cell", lf_) || !cell_layout_ok("examg_prolong_add_cell", lc_)) return 1;
-  if (lf_->nd != lc_->nd || lf_->nd < 2) { set_error("examg_prolong_add_cell: 2-D or 3-D layouts of one dimensionality"); return 1; }
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   const int nd = lf_->nd;

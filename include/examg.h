@@ -244,7 +244,11 @@ int examg_two_stage_eligible(const examg_layout_t *lu, const examg_layout_t *lf,
  * box, whose fine footprint must lie inside it (a block without neighbours; with neighbours the restriction reads residuals
  * on ghost points, which only an exchange of the stored field provides -- use the two calls).  3-D 7-point constant
  * stencils on long rows take the fused kernel and never touch `res`/`lr` (may be NULL); everything else runs
- * examg_residual + examg_restrict through `res`.  Bit-identical to the two calls either way. */
+ * examg_residual + examg_restrict through `res`.  Bit-identical to the two calls either way.
+ * The fallback is exactly those two calls with their contracts: `res` receives the residual on [fbegin, fend) and is read on the
+ * fine footprint [2 * cbegin - 1, 2 * (cend - 1) + 1] of the restriction, which must lie in its allocation `lr` (points of the
+ * footprint outside [fbegin, fend) are read as `res` holds them); `lr` and `res` are then required (an error without them).
+ * Either way only the box [cbegin, cend) of fc is written, u and rhs are not modified, and no two arrays may overlap. */
 int examg_residual_restrict(const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs,
                             const examg_layout_t *lr, double *res, const examg_stencil_t *st, const examg_layout_t *lc,
                             double *fc, double scale, const int32_t *fbegin, const int32_t *fend, const int32_t *cbegin,
@@ -255,14 +259,30 @@ int examg_residual_restrict_one_pass(const examg_layout_t *lu, const examg_layou
 
 /* ---- K4: RHS@coarser = scale * R * Residual, R = kron [1/4 1/2 1/4]
  * (operator/l4/L4_DefaultRestriction.scala:29-36,63-88; solver/ir/IR_ResolveIntergridIndices.scala);
- * begin/end: coarse iterator box. */
+ * begin/end: coarse iterator box.  For every coarse point I of the box
+ *   rhs_coarse(I) = sum over o in {-1, 0, 1}^d of (scale * ((w(o0) * w(o1)) * w(o2))) * res_fine(2I + o),   w = 1/4, 1/2, 1/4
+ * the terms added in entry order of the composed stencil: the x offset outermost, then y, then z, each -1, 0, +1 (2-D: no z
+ * factor and no z offset; dim 2 of the box is [0, 1)).
+ * Footprints: the box must lie in the coarse allocation and the fine points [2 * begin - 1, 2 * (end - 1) + 1] of every dimension
+ * of the layouts in the fine allocation (ghost and pad points count) -- else an error, and nothing is launched.  A box that holds
+ * the duplicate points of a block with neighbours (begin 0 or end = cells + 1) reads the fine ghost layer.
+ * Writes the box of rhs_coarse and nothing else; res_fine is not modified.  The two arrays must not overlap.  Either layout
+ * may be colour-split (EXAMG_LAYOUT_SPLIT_X); nd must be 2 or 3.  An empty box is a no-op that returns 0. */
 int examg_restrict(const examg_layout_t *lfine, const double *res_fine, const examg_layout_t *lcoarse,
                    double *rhs_coarse, double scale, const int32_t *begin, const int32_t *end,
                    examg_stream_t stream);
 
 /* ---- K5: Solution += P@coarser * Solution@coarser, P = 2^d R^T
  * (operator/l4/L4_DefaultProlongation.scala:30-45; parity cases
- * stencil/ir/IR_FindStencilConvolutions.scala:135-156); begin/end: fine iterator box. */
+ * stencil/ir/IR_FindStencilConvolutions.scala:135-156); begin/end: fine iterator box.  Per dimension an even fine index i takes
+ * the coarse point i / 2 with weight 1, an odd one (i + 1) / 2 and then (i - 1) / 2 with weight 1/2 each:
+ *   u_fine(i) = u_fine(i) + (sum of ((w0 * w1) * w2) * u_coarse(c0, c1, c2))
+ * the terms added with the x entry outermost, then y, then z, the upper coarse neighbour first.
+ * Footprints: the box must lie in the fine allocation, its indices must not be negative (the parity cases are those of the
+ * reference's loop, which starts at the lower duplicate point 0), and the coarse points [begin / 2, end / 2] of every dimension
+ * of the layouts must lie in the coarse allocation -- else an error, and nothing is launched.
+ * Writes the box of u_fine and nothing else; u_coarse is not modified.  The two arrays must not overlap.  Either layout may
+ * be colour-split; nd must be 2 or 3.  An empty box is a no-op that returns 0. */
 int examg_prolong_add(const examg_layout_t *lcoarse, const double *u_coarse, const examg_layout_t *lfine,
                       double *u_fine, const int32_t *begin, const int32_t *end, examg_stream_t stream);
 
@@ -572,14 +592,24 @@ int examg_apply_bc_cell(const examg_layout_t *l, double *x, const examg_geom_t *
 
 /* RHS@coarser = scale * R * Residual with R the linear cell restriction (operator/l4/L4_DefaultRestriction.scala:37-43,63-90):
  * kron over the dimensions of [2i -> 0.5, 2i+1 -> 0.5], the mean of the 2^d child cells, weight 0.5^d exactly.
- *   fc(I) = sum over the children, in entry order of the composed stencil (x offset outermost, then y, then z),
- *           of (scale * 0.5^d) * rf(2I + o)
- * begin/end: coarse iterator box.  Reads no ghost cell. */
+ *   fc(I) = sum over the children o in {0, 1}^d, in entry order of the composed stencil (x offset outermost, then y, then z, each
+ *           0 before 1), of (scale * 0.5^d) * rf(2I + o)
+ * begin/end: coarse iterator box (2-D: [0, 1) in dim 2).  Footprints: the box must lie in the coarse allocation and the fine
+ * cells [2 * begin, 2 * end) in the fine allocation -- else an error, and nothing is launched.  It reads exactly the children of
+ * the box's cells: no ghost cell unless the box holds coarse ghost cells.  Writes the box of fc and nothing else; rf is not
+ * modified; the arrays must not overlap.  Both layouts are cell layouts of one dimensionality (2 or 3): no duplicate layers,
+ * and no layout transformation (a colour-split cell layout is an error).  An empty box is a no-op that returns 0.
+ * Fine rows whose pairs (2I, 2I+1) are 16-byte aligned (FieldLayout.cell(..., align=2)) are read 16 bytes at a time, others 8:
+ * the same bits either way. */
 int examg_restrict_cell(const examg_layout_t *lfine, const double *rf, const examg_layout_t *lcoarse, double *fc, double scale,
                         const int32_t *begin, const int32_t *end, examg_stream_t stream);
 
 /* Solution += P@coarser * Solution@coarser with P = 2^d R^T (operator/l4/L4_DefaultProlongation.scala:30-45): every fine cell
- * receives 1.0 * its parent, uf(i) = uf(i) + uc(floor(i / 2)) -- piecewise-constant injection.  begin/end: fine iterator box. */
+ * receives 1.0 * its parent, uf(i) = uf(i) + uc(floor(i / 2)) -- piecewise-constant injection; floor also for the negative
+ * indices of ghost cells (cell -1 has the parent -1).  begin/end: fine iterator box (2-D: [0, 1) in dim 2).  Footprints: the
+ * box must lie in the fine allocation and the parents [floor(begin / 2), floor((end - 1) / 2)] in the coarse allocation -- else
+ * an error, and nothing is launched.  Writes the box of uf and nothing else; uc is not modified; the arrays must not overlap.
+ * Layouts as for examg_restrict_cell.  An empty box is a no-op that returns 0. */
 int examg_prolong_add_cell(const examg_layout_t *lcoarse, const double *uc, const examg_layout_t *lfine, double *uf,
                            const int32_t *begin, const int32_t *end, examg_stream_t stream);
 

@@ -645,3 +645,108 @@ def init_helmholtz27_ref(lc, cf, geom, a, ksq, begin, end):
                 else:
                     CF[ent][b] = c
                     ent += 1
+
+
+# -- cell transfers, exact (include/examg.h: examg_restrict_cell / examg_prolong_add_cell) -------------------------------------------
+def _exact_restrict_cell(self, lfine, rf, lc, fc, scale, begin, end):
+    """fc(I) = scale * 2^-d * (sum of the 2^d children rf(2I + o), o in {0, 1}^d), straight from the definition."""
+    if any(end[d] <= begin[d] for d in range(3)):
+        return
+    Lf, Lc = _Lay(lfine), _Lay(lc)
+    nd = Lf.nd
+    if Lc.nd != nd or (nd == 2 and (begin[2] != 0 or end[2] != 1)):
+        raise ValueError("cell restriction: layouts of one dimensionality, a 2-D box with [0, 1) in dim 2")
+    R = self._v(rf, lfine)
+    children = [(a, b, c) for a in (0, 1) for b in (0, 1) for c in ((0, 1) if nd == 3 else (0,))]
+    terms = [_mul(R[Lf.box(begin, end, o, step=2)], scale * 0.5 ** nd) for o in children]
+    self._v(fc, lc)[Lc.box(begin, end)] = _sum(terms)
+
+
+def _exact_prolong_add_cell(self, lc, uc, lfine, uf, begin, end):
+    """uf(i) += uc(floor(i / 2)); numpy's // floors negative indices too."""
+    if any(end[d] <= begin[d] for d in range(3)):
+        return
+    Lc, Lf = _Lay(lc), _Lay(lfine)
+    nd = Lf.nd
+    if Lc.nd != nd or (nd == 2 and (begin[2] != 0 or end[2] != 1)):
+        raise ValueError("cell prolongation: layouts of one dimensionality, a 2-D box with [0, 1) in dim 2")
+    idx = []
+    for d in (2, 1, 0):
+        i = np.arange(begin[d], end[d])
+        p = (i // 2 if d < nd else i) + Lc.ref[d]
+        if p.min() < 0 or p.max() >= Lc.tot[d]:
+            raise IndexError("parent cells leave the coarse allocation in dim %d" % d)
+        idx.append(p)
+    fb = Lf.box(begin, end)
+    Uf = self._v(uf, lfine)
+    Uf[fb] = _check(Uf[fb] + self._v(uc, lc)[np.ix_(*idx)])
+
+
+ExactOps.restrict_cell = _exact_restrict_cell
+ExactOps.prolong_add_cell = _exact_prolong_add_cell
+
+
+# -- transfer cases: geometry, linear fields, the adjoint identity --------------------------------------------------------------------
+def restrict_geometry(nd, n, kind):
+    """(fine cells, coarse cells, begin, end) of a node restriction whose coarse box has the extents n[0] x n[1] (x n[2]).
+    inner: the inner points [1, cells); faces: a block with neighbours -- x over both duplicate planes (begin 0, end cells + 1), y
+    over the lower one, z over the upper one, the fine footprint in the ghost layer there; inside_odd / inside_even: strictly inside
+    the inner points, begin (3, 2, 1) / (2, 1, 3)."""
+    lo = {"inner": (1, 1, 1), "faces": (0, 0, 1), "inside_odd": (3, 2, 1), "inside_even": (2, 1, 3)}[kind]
+    top = {"inner": (0, 0, 0), "faces": (-1, 0, -1), "inside_odd": (1, 2, 1), "inside_even": (2, 1, 1)}[kind]      # cells - end
+    b = [lo[d] if d < nd else 0 for d in range(3)]
+    e = [b[d] + n[d] if d < nd else 1 for d in range(3)]
+    cs = tuple(e[d] + top[d] if d < nd else 0 for d in range(3))
+    return tuple(2 * c for c in cs), cs, b, e
+
+
+def linear_field(l, coef, const=0, mul=1, add=0):
+    """Host float64 array over the whole allocation of `l`: sum_d coef[d] * (mul * i_d + add) + const at iterator point i (integer
+    arguments: exact).  Dimensions the layout does not have contribute nothing."""
+    L = _Lay(l)
+    ax = [np.arange(L.tot[d], dtype=np.int64) - L.ref[d] for d in range(3)]
+    v = np.full(L.shape, int(const), dtype=np.int64)
+    for d in range(L.nd):
+        sh = [1, 1, 1]
+        sh[2 - d] = -1
+        v = v + (int(coef[d]) * (int(mul) * ax[d] + int(add))).reshape(sh)
+    return v.astype(np.float64).reshape(-1)
+
+
+LINEAR = (3, 7, 11)          # pairwise distinct and coprime: no two axes, and no axis and its mirror, give the same field
+
+
+def box_values(l, a, b, e):
+    return np.asarray(a).reshape(_Lay(l).shape)[_Lay(l).box(b, e)]
+
+
+def supported_int_field(l, b, e, seed, lo=-9, hi=9):
+    """Host array: small integers inside the box, zero elsewhere."""
+    L = _Lay(l)
+    a = np.zeros(L.shape)
+    s = L.box(b, e)
+    a[s] = np.random.default_rng(seed).integers(lo, hi + 1, size=a[s].shape)
+    return a.reshape(-1)
+
+
+def transfer_adjoint(ops, cell, lf, lc, cb, ce, fb, fe, scale, seed):
+    """(sum(fc * w) * 2^d, scale * sum(r * P w)), both times a common power of two, in int64 for r supported in the fine box, w in the coarse box: equal,
+    because the restriction is scale * 2^-d * P^T.  Both operators run on kernel layer `ops`."""
+    nd = lf.nd
+    r, w = supported_int_field(lf, fb, fe, seed), supported_int_field(lc, cb, ce, seed + 1)
+    fc, pw = ops.from_host(np.zeros(lc.size)), ops.from_host(np.zeros(lf.size))
+    if cell:
+        ops.restrict_cell(lf.c_struct(), ops.from_host(r.copy()), lc.c_struct(), fc, scale, cb, ce)
+        ops.prolong_add_cell(lc.c_struct(), ops.from_host(w.copy()), lf.c_struct(), pw, fb, fe)
+    else:
+        ops.restrict(lf.c_struct(), ops.from_host(r.copy()), lc.c_struct(), fc, scale, cb, ce)
+        ops.prolong_add(lc.c_struct(), ops.from_host(w.copy()), lf.c_struct(), pw, fb, fe)
+    ops.synchronize()
+    # node: the full-weighting entries are multiples of 4^-d, the interpolation's of 2^-d; cell: 2^-d and 1
+    kf, kp = (2 ** nd, 1) if cell else (4 ** nd, 2 ** nd)
+    fck, pwk = np.asarray(ops.to_host(fc)) * kf, np.asarray(ops.to_host(pw)) * kp
+    assert np.array_equal(fck, np.round(fck)) and np.array_equal(pwk, np.round(pwk)) and float(scale) == int(scale)
+    lhs = int(np.sum(fck.astype(np.int64) * w.astype(np.int64))) * 2 ** nd * kp
+    rhs = int(scale) * int(np.sum(r.astype(np.int64) * pwk.astype(np.int64))) * kf
+    assert lhs != 0
+    return lhs, rhs

@@ -620,3 +620,161 @@ def test_oracle_init_helmholtz27_equals_the_definition(orc):
             if o[d]:
                 mir = tuple(-v if i == d else v for i, v in enumerate(o))
                 assert not np.array_equal(W[offs.index(o)][m], W[offs.index(mir)][m])
+
+
+# -- inter-grid transfers: the cell restatement and the oracle against the exact reference, closed forms, adjointness ---------------
+from cell_ops import CellOracleOps  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def cellorc():
+    return CellOracleOps()
+
+
+# (nd, fine cells, fine ghost, fine align, coarse ghost, coarse align): ghost widths 0 / 1 / 2, the two layouts never alike
+CELL_LAYOUTS = [(3, (12, 10, 8), 1, 0, 0, 2), (3, (14, 8, 10), 2, 2, 1, 0), (3, (10, 12, 8), 0, 16, 2, 2), (2, (18, 12, 0), 1, 2, 2, 0),
+                (2, (12, 14, 0), 2, 0, 0, 16), (2, (16, 10, 0), 0, 0, 1, 2)]
+
+
+def _cell_pair(nd, n, gf, af, gc, ac):
+    lf = FieldLayout.cell(nd, n[:nd], gf, align=af)
+    lc = FieldLayout.cell(nd, [v // 2 for v in n[:nd]], gc, False, ac)
+    return lf, lc
+
+
+def _cell_boxes(nd, n, ghost, coarse):
+    """Boxes with odd and even begins and ends in every dimension: the whole field, and two inside it (a fine box may begin in the
+    ghost layer: negative indices)."""
+    m = [v // 2 if coarse else v for v in n[:nd]]
+    z = nd == 3
+    out = [([0, 0, 0], [m[0], m[1], m[2] if z else 1]), ([1, 2, 1 if z else 0], [m[0] - 2, m[1] - 1, m[2] - 1 if z else 1]),
+           ([2, 1, 2 if z else 0], [m[0] - 1, m[1] - 2, m[2] - 1 if z else 1])]
+    if not coarse and ghost:
+        g = ghost
+        out.append(([-1, -g, -1 if z else 0], [m[0] + 1, m[1] - 1, m[2] + g if z else 1]))
+    assert all(e[d] > b[d] for b, e in out for d in range(3))
+    return out
+
+
+@pytest.mark.parametrize("scale", [1.0, 4.0, 0.25])
+@pytest.mark.parametrize("nd,n,gf,af,gc,ac", CELL_LAYOUTS)
+def test_cell_restatement_is_exact(cellorc, ex, nd, n, gf, af, gc, ac, scale):
+    """CellOracleOps.restrict_cell / prolong_add_cell (tests/cell_ops.py, the bitwise reference of the GPU tests) against the exact
+    reference written from the definitions: whole arrays, the inputs included; fine and coarse layouts differ in ghost and
+    alignment."""
+    lf, lc = _cell_pair(nd, n, gf, af, gc, ac)
+    for cb, ce in _cell_boxes(nd, n, gc, True):
+        def run(ops):
+            rf, fc = _fields(ops, (lf, lc), 30)
+            ops.restrict_cell(lf.c_struct(), rf, lc.c_struct(), fc, scale, cb, ce)
+            return _host(ops, (rf, fc))
+
+        _assert_equal(run(cellorc), run(ex), "restrict_cell %r %r" % (cb, ce))
+    for fb, fe in _cell_boxes(nd, n, min(gf, 2 * gc), False):
+        def run(ops):
+            uc, uf = _fields(ops, (lc, lf), 40)
+            ops.prolong_add_cell(lc.c_struct(), uc, lf.c_struct(), uf, fb, fe)
+            return _host(ops, (uc, uf))
+
+        _assert_equal(run(cellorc), run(ex), "prolong_add_cell %r %r" % (fb, fe))
+
+
+def test_exact_cell_transfers_refuse_what_leaves_the_allocation(ex):
+    lf, lc = _cell_pair(3, (8, 8, 8), 1, 0, 0, 0)
+    uc, uf = _fields(ex, (lc, lf), 1)
+    with pytest.raises(IndexError):          # fine cell -1 has parent -1: the coarse layout has no ghost layer
+        ex.prolong_add_cell(lc, uc, lf, uf, [-1, 0, 0], [8, 8, 8])
+    with pytest.raises(IndexError):
+        ex.restrict_cell(lf, uf, lc, uc, 1.0, [0, 0, 0], [5, 4, 4])
+
+
+# fine / coarse-rhs / coarse-solution layouts, each with its own ghost width and alignment
+NODE_LAYOUTS = [((2, 0), (0, 2), (1, 16)), ((1, 16), (2, 0), (0, 2)), ((1, 2), (1, 0), (2, 4))]
+
+
+def _node_triple(nd, fs, cs, lay):
+    (gf, af), (gr, ar), (gs, as_) = NODE_LAYOUTS[lay]
+    return (FieldLayout.node(nd, fs, gf, align=af), FieldLayout.node(nd, cs, gr, True, False, ar), FieldLayout.node(nd, cs, gs, align=as_))
+
+
+@pytest.mark.parametrize("scale", [1.0, 4.0])
+@pytest.mark.parametrize("lay", [0, 1, 2])
+@pytest.mark.parametrize("nd,n,kind", [(3, (9, 4, 6), "inner"), (3, (7, 5, 4), "faces"), (3, (6, 3, 5), "inside_odd"), (3, (5, 7, 3), "inside_even"),
+                                       (2, (9, 5, 0), "inner"), (2, (6, 8, 0), "faces"), (2, (7, 4, 0), "inside_odd")])
+def test_oracle_transfers_are_exact_on_anisotropic_shapes(orc, ex, nd, n, kind, lay, scale):
+    """orc_restrict / orc_prolong_add on boxes whose extents differ in every dimension, the fine, coarse-rhs and coarse-solution
+    arrays each in a layout of its own: whole arrays, inputs included."""
+    fs, cs, cb, ce = S.restrict_geometry(nd, n, kind)
+    lfi, lrh, lco = _node_triple(nd, fs, cs, lay)
+    # the prolongation box: the fine points of the restriction's footprint that have non-negative indices
+    fb = [max(2 * cb[d] - 1, 0) if d < nd else 0 for d in range(3)]
+    fe = [min(2 * ce[d], fs[d] + 1) if d < nd else 1 for d in range(3)]
+
+    def run(ops):
+        r, fc, uc, uf = _fields(ops, (lfi, lrh, lco, lfi), 50)
+        ops.restrict(lfi.c_struct(), r, lrh.c_struct(), fc, scale, cb, ce)
+        ops.prolong_add(lco.c_struct(), uc, lfi.c_struct(), uf, fb, fe)
+        return _host(ops, (r, fc, uc, uf))
+
+    _assert_equal(run(orc), run(ex), "transfers %s" % kind)
+
+
+def _layers(orc, cellorc, ex, cell):
+    return [cellorc if cell else orc, ex]
+
+
+@pytest.mark.parametrize("scale", [1.0, 4.0])
+@pytest.mark.parametrize("nd,n,kind,lay", [(3, (9, 4, 6), "inner", 0), (3, (7, 5, 4), "faces", 1), (3, (5, 7, 3), "inside_even", 2),
+                                           (2, (9, 5, 0), "inner", 1), (2, (6, 8, 0), "faces", 0)])
+def test_node_transfers_of_linear_fields_have_closed_forms(orc, cellorc, ex, nd, n, kind, lay, scale):
+    """v = 3 i + 7 j + 11 k + 5: full weighting gives scale * v(2I); interpolating uc(I) = v(2I) onto zeros gives v.  Plain float64
+    numpy with equality, on the oracle and on the exact reference."""
+    fs, cs, cb, ce = S.restrict_geometry(nd, n, kind)
+    lfi, lrh, lco = _node_triple(nd, fs, cs, lay)
+    fb = [max(2 * cb[d] - 1, 0) if d < nd else 0 for d in range(3)]
+    fe = [min(2 * ce[d], fs[d] + 1) if d < nd else 1 for d in range(3)]
+    for ops in _layers(orc, cellorc, ex, False):
+        fc, uf = ops.from_host(np.zeros(lrh.size)), ops.from_host(np.zeros(lfi.size))
+        ops.restrict(lfi.c_struct(), ops.from_host(S.linear_field(lfi, S.LINEAR, 5)), lrh.c_struct(), fc, scale, cb, ce)
+        ops.prolong_add(lco.c_struct(), ops.from_host(S.linear_field(lco, S.LINEAR, 5, mul=2)), lfi.c_struct(), uf, fb, fe)
+        assert np.array_equal(S.box_values(lrh, ops.to_host(fc), cb, ce), scale * S.box_values(lrh, S.linear_field(lrh, S.LINEAR, 5, mul=2), cb, ce))
+        assert np.array_equal(S.box_values(lfi, ops.to_host(uf), fb, fe), S.box_values(lfi, S.linear_field(lfi, S.LINEAR, 5), fb, fe))
+
+
+@pytest.mark.parametrize("scale", [1.0, 4.0, 0.25])
+@pytest.mark.parametrize("nd,n,gf,af,gc,ac", CELL_LAYOUTS)
+def test_cell_transfers_of_linear_fields_have_closed_forms(orc, cellorc, ex, nd, n, gf, af, gc, ac, scale):
+    """Fine values 2 v at the cell centres (2 v(i + 1/2) = 3 (2 i + 1) + ..: integers): the mean of the children is 2 v at the
+    parent's centre, 3 (4 I + 2) + ..; the prolongation of a linear coarse field onto zeros gives uc(i >> 1)."""
+    lf, lc = _cell_pair(nd, n, gf, af, gc, ac)
+    for ops in _layers(orc, cellorc, ex, True):
+        for cb, ce in _cell_boxes(nd, n, gc, True):
+            fc = ops.from_host(np.zeros(lc.size))
+            ops.restrict_cell(lf.c_struct(), ops.from_host(S.linear_field(lf, S.LINEAR, 10, mul=2, add=1)), lc.c_struct(), fc, scale, cb, ce)
+            assert np.array_equal(S.box_values(lc, ops.to_host(fc), cb, ce), scale * S.box_values(lc, S.linear_field(lc, S.LINEAR, 10, mul=4, add=2), cb, ce))
+        for fb, fe in _cell_boxes(nd, n, min(gf, 2 * gc), False):
+            uf = ops.from_host(np.zeros(lf.size))
+            ops.prolong_add_cell(lc.c_struct(), ops.from_host(S.linear_field(lc, S.LINEAR, 4)), lf.c_struct(), uf, fb, fe)
+            idx = np.meshgrid(*[np.arange(fb[d], fe[d]) >> (1 if d < nd else 0) for d in (2, 1, 0)], indexing="ij")
+            want = 4 + sum(S.LINEAR[d] * idx[2 - d] for d in range(nd))
+            assert np.array_equal(S.box_values(lf, ops.to_host(uf), fb, fe), want.astype(np.float64))
+
+
+@pytest.mark.parametrize("scale", [1.0, 4.0])
+def test_restriction_is_the_scaled_adjoint_of_the_prolongation(orc, cellorc, ex, scale):
+    """sum(fc * w) * 2^d == scale * sum(r * P w) for integer fields that vanish outside the boxes, in int64."""
+    for nd, n, kind, lay in [(3, (9, 4, 6), "inner", 0), (3, (7, 5, 4), "faces", 1), (2, (9, 5, 0), "inside_odd", 2)]:
+        fs, cs, cb, ce = S.restrict_geometry(nd, n, kind)
+        lfi, lrh, _ = _node_triple(nd, fs, cs, lay)
+        fb = [max(2 * cb[d] - 1, 0) if d < nd else 0 for d in range(3)]
+        fe = [min(2 * ce[d], fs[d] + 1) if d < nd else 1 for d in range(3)]
+        for ops in (orc, ex):
+            lhs, rhs = S.transfer_adjoint(ops, False, lfi, lrh, cb, ce, fb, fe, scale, 60)
+            assert lhs == rhs
+    for nd, n, gf, af, gc, ac in CELL_LAYOUTS:
+        lf, lc = _cell_pair(nd, n, gf, af, gc, ac)
+        cb, ce = _cell_boxes(nd, n, gc, True)[1]
+        fb, fe = _cell_boxes(nd, n, min(gf, 2 * gc), False)[-1]
+        for ops in (cellorc, ex):
+            lhs, rhs = S.transfer_adjoint(ops, True, lf, lc, cb, ce, fb, fe, scale, 70)
+            assert lhs == rhs

@@ -74,11 +74,21 @@ struct Box {
   __host__ __device__ long long count() const {
     return (n0() <= 0 || n1() <= 0 || n2() <= 0) ? 0 : (long long)n0() * n1() * n2();
   }
+  bool operator==(const Box &o) const { return b0 == o.b0 && b1 == o.b1 && b2 == o.b2 && e0 == o.e0 && e1 == o.e1 && e2 == o.e2; }
+  bool contains(const Box &o) const { return o.b0 >= b0 && o.b1 >= b1 && o.b2 >= b2 && o.e0 <= e0 && o.e1 <= e1 && o.e2 <= e2; }
 };
 
 static inline Box make_box(const int32_t *begin, const int32_t *end) {
   Box b{begin[0], begin[1], begin[2], end[0], end[1], end[2]};
   return b;
+}
+
+// [begin,end) grown by `reach` points in the first nd dimensions: a box with its shell of that depth
+static inline void grow_box(const int32_t *begin, const int32_t *end, int reach, int nd, int32_t *gbegin, int32_t *gend) {
+  for (int d = 0; d < 3; ++d) {
+    gbegin[d] = begin[d] - (d < nd ? reach : 0);
+    gend[d] = end[d] + (d < nd ? reach : 0);
+  }
 }
 
 // Does the box (grown by `halo` points, in iterator coords) stay inside the allocation?

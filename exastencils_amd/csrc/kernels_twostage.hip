@@ -696,9 +696,10 @@ static bool prolong_args_ok(const char *who, const examg_layout_t *lc, const Box
   return true;
 }
 
+// (plane strides below 2^32 elements: the kernels form the offset of a row within a plane as a 32-bit product)
 static bool two_stage_ok(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const Box &box) {
   return !g_ts_disable && !lay_split(lu) && !lay_split(lf) && lu->nd == 3 && canonical_order7(st) >= 0 && box.n0() >= 64 && box_inside(lu, box, 1) &&
-         box_inside(lf, box, 0);
+         box_inside(lf, box, 0) && make_layout(lu).s2 < (1LL << 32) && make_layout(lf).s2 < (1LL << 32);
 }
 
 // Separate stage boxes: the 16-byte loads of the kernel read the first (last) element of the rhs array as the second (first) half of
@@ -1022,9 +1023,7 @@ static thread_local long long g_ts3_minpts = 8000000LL;      // examg_debug_thre
 // stages is faster (traced V-cycle, 128^3: two passes of three colour loops 43 + 41 us against three sweeps of 15-20 us; 256^3: 2 x 0.110 ms
 // against 3 x 0.094)
 static bool three_stage_ok(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const Box &box) {
-  if (g_ts3_disable || !two_stage_ok(lu, lf, st, box) || box.n1() < 20 || box.count() < g_ts3_minpts) return false;
-  const LayoutDev u = make_layout(lu), f = make_layout(lf);
-  return u.s2 < (1LL << 32) && f.s2 < (1LL << 32);
+  return !g_ts3_disable && two_stage_ok(lu, lf, st, box) && box.n1() >= 20 && box.count() >= g_ts3_minpts;
 }
 
 template <int NW, int RPW, bool COL>
@@ -1130,50 +1129,101 @@ extern "C" int examg_debug_two_stage(int disable, int blocks, int remap, int wy)
 }
 #endif
 
-// Will examg_jacobi2_boxes / examg_rbgs_sweep_fused_boxes take the one-pass kernel for these arguments (1) or their
-// fallback through `tmp` (0)?  The ONE place this is decided: callers that overlap the pass with work on another stream ask
-// here, because the fallback writes `tmp` on the launch stream.
+// ---------------------------------------------------------------------------------------------------------------
+// The one-pass smoother entry points.  Each one checks its arguments (args_ok), asks two_stage_route which one-pass kernel
+// takes them, launches that kernel (launch_route) or runs its fallback of plain loops.  examg_two_stage_eligible is
+// `two_stage_route(...) != ROUTE_NONE`, so what the query promises and what an entry point does agree by construction.
+// ---------------------------------------------------------------------------------------------------------------
+enum Route { ROUTE_NONE = 0, ROUTE_LDS, ROUTE_SMALL };
+
+// Which one-pass kernel runs stage 1 on box 1 and stage 2 on box 2 (the one-box forms: box 1 = box 2)?  The two-stage LDS
+// kernel (rows of at least 64 points, canonical 7-point orders, both boxes inside the allocations, plane strides below 2^32
+// elements), the small-level kernel (shorter rows, one box only: kernels_small.hip), or none: the entry point's fallback.
+// The record pair of kernels_sf27pair.hip is not a route: the Jacobi-pair forms try it after this answered "none".
+static Route two_stage_route(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const Box &box1, const Box &box2) {
+  if (box2.count() == 0 || !box1.contains(box2)) return ROUTE_NONE;
+  if (two_stage_ok(lu, lf, st, box2) && box_inside(lu, box1, 1) && box_inside(lf, box1, 0) && stage_boxes_ok(lf, box1, box2)) return ROUTE_LDS;
+  if (box1 == box2 && small_two_stage_ok(lu, lf, st, box2)) return ROUTE_SMALL;
+  return ROUTE_NONE;
+}
+
+// The kernel of route r (not ROUTE_NONE).  var as in launch_small_two_stage: 0 plain, 1 the correction from (lc, uc) folded in,
+// 2 zero input (u_in is not read)
+template <bool COL>
+static int launch_route(Route r, const char *who, const examg_layout_t *lu, const double *u_in, double *u_out, const examg_layout_t *lf,
+                        const double *rhs, const examg_stencil_t *st, double w, int first, const Box &box1, const Box &box2, int var,
+                        const examg_layout_t *lc, const double *uc, hipStream_t s) {
+  if (var == 1 && !prolong_args_ok(who, lc, box2)) return 1;
+  if (r == ROUTE_SMALL) return launch_small_two_stage(COL, var, lu, u_in, u_out, lf, rhs, st, w, first, box2, lc, uc, s);
+  TSProl pr;
+  if (var == 1) pr = TSProl{make_layout(lc), uc};
+  return launch_two_stage<COL>(lu, var == 2 ? u_out : u_in, lf, rhs, u_out, st, w, first, box2, s, &box1, var == 1 ? &pr : nullptr, var == 2);
+}
+
+// The checks every entry point starts with; `given`: no pointer argument is null.  The Jacobi forms pass first = 0, the
+// zero-field form u_in = nullptr.
+static bool args_ok(const char *who, bool given, const void *u_in, const void *u_out, int first) {
+  if (!given) { set_error("%s: null argument", who); return false; }
+  if (u_in == u_out) { set_error("%s: out of place only", who); return false; }
+  if (first != 0 && first != 1) { set_error("%s: first colour must be 0 or 1", who); return false; }
+  return true;
+}
+
+// ... and the one a fallback through `tmp` starts with
+static bool tmp_ok(const char *who, const void *tmp, const void *u_in, const void *u_out) {
+  if (!tmp || tmp == u_in || tmp == u_out) { set_error("%s: fallback needs a distinct tmp array", who); return false; }
+  return true;
+}
+
+// Fallback of the colour-loop forms (general stencils / small boxes): u_in's values -- zeros where u_in is null -- on the box
+// and its one-stencil-reach shell of u_out, the correction where uc is given, then n colour loops in place on that copy,
+// colour `first` first (the shell of u_out keeps what the copy put there -- see the header)
+static int colour_loops_on_copy(const examg_layout_t *lu, const double *u_in, double *u_out, const examg_layout_t *lc, const double *uc,
+                                const examg_layout_t *lf, const double *rhs, const examg_stencil_t *st, double w, int first, int n,
+                                const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  int32_t gb[3], ge[3];
+  grow_box(begin, end, stencil_reach(st), lu->nd, gb, ge);
+  int rc = u_in ? examg_axpby(lu, u_in, lu, u_out, 1.0, 0.0, gb, ge, stream) : examg_set(lu, u_out, 0.0, gb, ge, stream);
+  if (!rc && uc) rc = examg_prolong_add(lc, uc, lu, u_out, begin, end, stream);
+  for (int k = 0; k < n && !rc; ++k) rc = examg_rbgs_colour(lu, u_out, lf, rhs, st, w, (k & 1) ? 1 - first : first, begin, end, stream);
+  return rc;
+}
+
+// Fallback of the Jacobi forms: box 1 with its shell (Dirichlet / halo values for the steps behind) into tmp, a step
+// u_in -> tmp on box 1 and, where u_out is given, a step tmp -> u_out on box 2
+static int jacobi_through_tmp(const examg_layout_t *lu, const double *u_in, double *u_out, double *tmp, const examg_layout_t *lf,
+                              const double *rhs, const examg_stencil_t *st, double w, const int32_t *begin1, const int32_t *end1,
+                              const int32_t *begin2, const int32_t *end2, examg_stream_t stream) {
+  int32_t gb[3], ge[3];
+  grow_box(begin1, end1, stencil_reach(st), lu->nd, gb, ge);
+  int rc = examg_axpby(lu, u_in, lu, tmp, 1.0, 0.0, gb, ge, stream);
+  if (!rc) rc = examg_jacobi(lu, u_in, tmp, lf, rhs, st, w, begin1, end1, stream);
+  if (!rc && u_out) rc = examg_jacobi(lu, tmp, u_out, lf, rhs, st, w, begin2, end2, stream);
+  return rc;
+}
+
+// Will examg_jacobi2_boxes / examg_rbgs_sweep_fused_boxes take a one-pass kernel for these arguments (1) or their fallback
+// through `tmp` (0)?  Callers that overlap the pass with work on another stream, or that pass no `tmp`, ask here: the
+// fallback writes `tmp` on the launch stream.  The answer is two_stage_route's, on which every entry point below switches.
+// A layout with planes of 2^32 elements or more is answered 0 and takes the fallback in every entry point (two_stage_ok holds
+// the bound; the launcher's own test of it is a defensive error that no entry point reaches).
 extern "C" int examg_two_stage_eligible(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st,
                                         const int32_t *begin1, const int32_t *end1, const int32_t *begin2, const int32_t *end2) {
   if (!lu || !lf || !st || !begin1 || !end1 || !begin2 || !end2) return 0;
-  const Box box1 = make_box(begin1, end1), box2 = make_box(begin2, end2);
-  if (box2.count() == 0) return 0;
-  if (box2.b0 < box1.b0 || box2.b1 < box1.b1 || box2.b2 < box1.b2 || box2.e0 > box1.e0 || box2.e1 > box1.e1 || box2.e2 > box1.e2) return 0;
-  // launch-bound levels (rows shorter than 64 points): the small-level sweep, one box only (kernels_small.hip)
-  if (box1.b0 == box2.b0 && box1.b1 == box2.b1 && box1.b2 == box2.b2 && box1.e0 == box2.e0 && box1.e1 == box2.e1 && box1.e2 == box2.e2 &&
-      small_two_stage_ok(lu, lf, st, box2))
-    return 1;
-  if (!(two_stage_ok(lu, lf, st, box2) && box_inside(lu, box1, 1) && box_inside(lf, box1, 0) && stage_boxes_ok(lf, box1, box2))) return 0;
-  // launch_two_stage_lds: row offsets within a plane are 32-bit products
-  const LayoutDev u = make_layout(lu), f = make_layout(lf);
-  return (u.s2 < (1LL << 32) && f.s2 < (1LL << 32)) ? 1 : 0;
+  return two_stage_route(lu, lf, st, make_box(begin1, end1), make_box(begin2, end2)) != ROUTE_NONE;
 }
 
 // One full red-black sweep, out of place.
 extern "C" int examg_rbgs_sweep_fused(const examg_layout_t *lu, const double *u_in, double *u_out,
                                       const examg_layout_t *lf, const double *rhs, const examg_stencil_t *st, double w,
                                       int first, const int32_t *begin, const int32_t *end, examg_stream_t stream) {
-  if (!lu || !u_in || !u_out || !lf || !rhs || !st || !begin || !end) { set_error("examg_rbgs_sweep_fused: null argument"); return 1; }
-  if (u_in == u_out) { set_error("examg_rbgs_sweep_fused: out of place only"); return 1; }
-  if (first != 0 && first != 1) { set_error("examg_rbgs_sweep_fused: first colour must be 0 or 1"); return 1; }
+  const char *who = "examg_rbgs_sweep_fused";
+  if (!args_ok(who, lu && u_in && u_out && lf && rhs && st && begin && end, u_in, u_out, first)) return 1;
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
-  if (two_stage_ok(lu, lf, st, box)) return launch_two_stage<true>(lu, u_in, lf, rhs, u_out, st, w, first, box, (hipStream_t)stream);
-  if (small_two_stage_ok(lu, lf, st, box)) return launch_small_two_stage(true, 0, lu, u_in, u_out, lf, rhs, st, w, first, box, nullptr, nullptr, (hipStream_t)stream);
-  // general stencils / small boxes: bring the box and its one-stencil-reach shell over, then the two half
-  // sweeps in place on the copy (the shell of u_out receives u_in's shell values -- see the header)
-  const int reach = stencil_reach(st);
-  int32_t b2[3], e2[3];
-  for (int d = 0; d < 3; ++d) {
-    const bool on = d < lu->nd;
-    b2[d] = begin[d] - (on ? reach : 0);
-    e2[d] = end[d] + (on ? reach : 0);
-  }
-  int rc = examg_axpby(lu, u_in, lu, u_out, 1.0, 0.0, b2, e2, stream);
-  if (rc) return rc;
-  rc = examg_rbgs_colour(lu, u_out, lf, rhs, st, w, first, begin, end, stream);
-  if (rc) return rc;
-  return examg_rbgs_colour(lu, u_out, lf, rhs, st, w, 1 - first, begin, end, stream);
+  if (const Route r = two_stage_route(lu, lf, st, box, box))
+    return launch_route<true>(r, who, lu, u_in, u_out, lf, rhs, st, w, first, box, box, 0, nullptr, nullptr, (hipStream_t)stream);
+  return colour_loops_on_copy(lu, u_in, u_out, nullptr, nullptr, lf, rhs, st, w, first, 2, begin, end, stream);
 }
 
 // One full red-black sweep of the ZERO field (every value of u, boundary planes included, is 0.0): u_out receives on the box
@@ -1181,26 +1231,13 @@ extern "C" int examg_rbgs_sweep_fused(const examg_layout_t *lu, const double *u_
 extern "C" int examg_rbgs_sweep_fused_zero(const examg_layout_t *lu, double *u_out, const examg_layout_t *lf, const double *rhs,
                                            const examg_stencil_t *st, double w, int first, const int32_t *begin,
                                            const int32_t *end, examg_stream_t stream) {
-  if (!lu || !u_out || !lf || !rhs || !st || !begin || !end) { set_error("examg_rbgs_sweep_fused_zero: null argument"); return 1; }
-  if (first != 0 && first != 1) { set_error("examg_rbgs_sweep_fused_zero: first colour must be 0 or 1"); return 1; }
+  const char *who = "examg_rbgs_sweep_fused_zero";
+  if (!args_ok(who, lu && u_out && lf && rhs && st && begin && end, nullptr, u_out, first)) return 1;
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
-  if (two_stage_ok(lu, lf, st, box))
-    return launch_two_stage<true>(lu, u_out, lf, rhs, u_out, st, w, first, box, (hipStream_t)stream, nullptr, nullptr, true);
-  if (small_two_stage_ok(lu, lf, st, box)) return launch_small_two_stage(true, 2, lu, nullptr, u_out, lf, rhs, st, w, first, box, nullptr, nullptr, (hipStream_t)stream);
-  // general stencils / small boxes: zero the box and its one-stencil-reach shell, then the two half sweeps in place
-  const int reach = stencil_reach(st);
-  int32_t b2[3], e2[3];
-  for (int d = 0; d < 3; ++d) {
-    const bool on = d < lu->nd;
-    b2[d] = begin[d] - (on ? reach : 0);
-    e2[d] = end[d] + (on ? reach : 0);
-  }
-  int rc = examg_set(lu, u_out, 0.0, b2, e2, stream);
-  if (rc) return rc;
-  rc = examg_rbgs_colour(lu, u_out, lf, rhs, st, w, first, begin, end, stream);
-  if (rc) return rc;
-  return examg_rbgs_colour(lu, u_out, lf, rhs, st, w, 1 - first, begin, end, stream);
+  if (const Route r = two_stage_route(lu, lf, st, box, box))
+    return launch_route<true>(r, who, lu, nullptr, u_out, lf, rhs, st, w, first, box, box, 2, nullptr, nullptr, (hipStream_t)stream);
+  return colour_loops_on_copy(lu, nullptr, u_out, nullptr, nullptr, lf, rhs, st, w, first, 2, begin, end, stream);
 }
 
 // `u += Prolongation * uc` on [begin,end) followed by one full red-black sweep on the same box, out of place: u_out receives
@@ -1209,37 +1246,13 @@ extern "C" int examg_rbgs_sweep_fused_prolong(const examg_layout_t *lu, const do
                                               const examg_layout_t *lf, const double *rhs, const examg_stencil_t *st, double w,
                                               int first, const int32_t *begin, const int32_t *end, const examg_layout_t *lc,
                                               const double *uc, examg_stream_t stream) {
-  if (!lu || !u_in || !u_out || !lf || !rhs || !st || !begin || !end || !lc || !uc) { set_error("examg_rbgs_sweep_fused_prolong: null argument"); return 1; }
-  if (u_in == u_out) { set_error("examg_rbgs_sweep_fused_prolong: out of place only"); return 1; }
-  if (first != 0 && first != 1) { set_error("examg_rbgs_sweep_fused_prolong: first colour must be 0 or 1"); return 1; }
+  const char *who = "examg_rbgs_sweep_fused_prolong";
+  if (!args_ok(who, lu && u_in && u_out && lf && rhs && st && begin && end && lc && uc, u_in, u_out, first)) return 1;
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
-  if (two_stage_ok(lu, lf, st, box)) {
-    if (!prolong_args_ok("examg_rbgs_sweep_fused_prolong", lc, box)) return 1;
-    TSProl pr;
-    pr.lc = make_layout(lc);
-    pr.uc = uc;
-    return launch_two_stage<true>(lu, u_in, lf, rhs, u_out, st, w, first, box, (hipStream_t)stream, nullptr, &pr);
-  }
-  if (small_two_stage_ok(lu, lf, st, box)) {
-    if (!prolong_args_ok("examg_rbgs_sweep_fused_prolong", lc, box)) return 1;
-    return launch_small_two_stage(true, 1, lu, u_in, u_out, lf, rhs, st, w, first, box, lc, uc, (hipStream_t)stream);
-  }
-  // general stencils / small boxes: the three loops one after the other on a copy (box + one-stencil-reach shell)
-  const int reach = stencil_reach(st);
-  int32_t b2[3], e2[3];
-  for (int d = 0; d < 3; ++d) {
-    const bool on = d < lu->nd;
-    b2[d] = begin[d] - (on ? reach : 0);
-    e2[d] = end[d] + (on ? reach : 0);
-  }
-  int rc = examg_axpby(lu, u_in, lu, u_out, 1.0, 0.0, b2, e2, stream);
-  if (rc) return rc;
-  rc = examg_prolong_add(lc, uc, lu, u_out, begin, end, stream);
-  if (rc) return rc;
-  rc = examg_rbgs_colour(lu, u_out, lf, rhs, st, w, first, begin, end, stream);
-  if (rc) return rc;
-  return examg_rbgs_colour(lu, u_out, lf, rhs, st, w, 1 - first, begin, end, stream);
+  if (const Route r = two_stage_route(lu, lf, st, box, box))
+    return launch_route<true>(r, who, lu, u_in, u_out, lf, rhs, st, w, first, box, box, 1, lc, uc, (hipStream_t)stream);
+  return colour_loops_on_copy(lu, u_in, u_out, lc, uc, lf, rhs, st, w, first, 2, begin, end, stream);
 }
 
 // One red-black sweep with separate boxes (blocks with neighbours): colour `first` on [begin1,end1) (points outside keep
@@ -1248,36 +1261,37 @@ extern "C" int examg_rbgs_sweep_fused_boxes(const examg_layout_t *lu, const doub
                                             const examg_layout_t *lf, const double *rhs, const examg_stencil_t *st, double w,
                                             int first, const int32_t *begin1, const int32_t *end1, const int32_t *begin2,
                                             const int32_t *end2, examg_stream_t stream) {
-  if (!lu || !u_in || !u_out || !lf || !rhs || !st || !begin1 || !end1 || !begin2 || !end2) { set_error("examg_rbgs_sweep_fused_boxes: null argument"); return 1; }
-  if (u_in == u_out) { set_error("examg_rbgs_sweep_fused_boxes: out of place only"); return 1; }
-  if (first != 0 && first != 1) { set_error("examg_rbgs_sweep_fused_boxes: first colour must be 0 or 1"); return 1; }
+  const char *who = "examg_rbgs_sweep_fused_boxes";
+  if (!args_ok(who, lu && u_in && u_out && lf && rhs && st && begin1 && end1 && begin2 && end2, u_in, u_out, first)) return 1;
   const Box box1 = make_box(begin1, end1), box2 = make_box(begin2, end2);
   if (box2.count() == 0) return 0;
-  if (box2.b0 < box1.b0 || box2.b1 < box1.b1 || box2.b2 < box1.b2 || box2.e0 > box1.e0 || box2.e1 > box1.e1 || box2.e2 > box1.e2) {
-    set_error("examg_rbgs_sweep_fused_boxes: the second box must lie inside the first");
-    return 1;
-  }
-  if (two_stage_ok(lu, lf, st, box2) && box_inside(lu, box1, 1) && box_inside(lf, box1, 0) && stage_boxes_ok(lf, box1, box2))
-    return launch_two_stage<true>(lu, u_in, lf, rhs, u_out, st, w, first, box2, (hipStream_t)stream, &box1);
-  if (box1.b0 == box2.b0 && box1.b1 == box2.b1 && box1.b2 == box2.b2 && box1.e0 == box2.e0 && box1.e1 == box2.e1 && box1.e2 == box2.e2 &&
-      small_two_stage_ok(lu, lf, st, box2))
-    return launch_small_two_stage(true, 0, lu, u_in, u_out, lf, rhs, st, w, first, box2, nullptr, nullptr, (hipStream_t)stream);
-  if (!tmp || tmp == u_in || tmp == u_out) { set_error("examg_rbgs_sweep_fused_boxes: fallback needs a distinct tmp array"); return 1; }
-  const int reach = stencil_reach(st);
-  int32_t b2[3], e2[3];
-  for (int d = 0; d < 3; ++d) {
-    const bool on = d < lu->nd;
-    b2[d] = begin1[d] - (on ? reach : 0);
-    e2[d] = end1[d] + (on ? reach : 0);
-  }
-  int rc = examg_axpby(lu, u_in, lu, tmp, 1.0, 0.0, b2, e2, stream);
-  if (rc) return rc;
-  rc = examg_rbgs_colour(lu, tmp, lf, rhs, st, w, first, begin1, end1, stream);     // in place on the copy
-  if (rc) return rc;
-  rc = examg_axpby(lu, tmp, lu, u_out, 1.0, 0.0, begin2, end2, stream);
-  if (rc) return rc;
+  if (!box1.contains(box2)) { set_error("%s: the second box must lie inside the first", who); return 1; }
+  if (const Route r = two_stage_route(lu, lf, st, box1, box2))
+    return launch_route<true>(r, who, lu, u_in, u_out, lf, rhs, st, w, first, box1, box2, 0, nullptr, nullptr, (hipStream_t)stream);
+  if (!tmp_ok(who, tmp, u_in, u_out)) return 1;
+  int32_t gb[3], ge[3];
+  grow_box(begin1, end1, stencil_reach(st), lu->nd, gb, ge);
+  int rc = examg_axpby(lu, u_in, lu, tmp, 1.0, 0.0, gb, ge, stream);
+  if (!rc) rc = examg_rbgs_colour(lu, tmp, lf, rhs, st, w, first, begin1, end1, stream);     // in place on the copy
+  if (!rc) rc = examg_axpby(lu, tmp, lu, u_out, 1.0, 0.0, begin2, end2, stream);
   // other colour: reads the copy, writes that colour's points of u_out
-  return examg_stencil_op(EXAMG_SMOOTH, lu, tmp, lf, rhs, lu, u_out, st, w, 1 - first, begin2, end2, stream);
+  if (!rc) rc = examg_stencil_op(EXAMG_SMOOTH, lu, tmp, lf, rhs, lu, u_out, st, w, 1 - first, begin2, end2, stream);
+  return rc;
+}
+
+// examg_jacobi2_boxes, and examg_jacobi2 with both boxes = [begin,end)
+static int jacobi2_boxes(const char *who, const examg_layout_t *lu, const double *u_in, double *u_out, double *tmp, const examg_layout_t *lf,
+                         const double *rhs, const examg_stencil_t *st, double w, const int32_t *begin1, const int32_t *end1,
+                         const int32_t *begin2, const int32_t *end2, examg_stream_t stream) {
+  if (!args_ok(who, lu && u_in && u_out && lf && rhs && st && begin1 && end1 && begin2 && end2, u_in, u_out, 0)) return 1;
+  const Box box1 = make_box(begin1, end1), box2 = make_box(begin2, end2);
+  if (box2.count() == 0) return 0;
+  if (!box1.contains(box2)) { set_error("%s: the stage-2 box must lie inside the stage-1 box", who); return 1; }
+  if (const Route r = two_stage_route(lu, lf, st, box1, box2))
+    return launch_route<false>(r, who, lu, u_in, u_out, lf, rhs, st, w, 0, box1, box2, 0, nullptr, nullptr, (hipStream_t)stream);
+  if (const int r27 = sf27_jacobi2_try(lu, u_in, u_out, lf, rhs, st, w, box1, box2, (hipStream_t)stream)) return r27 < 0 ? 1 : 0;
+  if (!tmp_ok(who, tmp, u_in, u_out)) return 1;
+  return jacobi_through_tmp(lu, u_in, u_out, tmp, lf, rhs, st, w, begin1, end1, begin2, end2, stream);
 }
 
 // Two Jacobi steps with separate boxes: stage 1 = J on [begin1,end1) (points outside keep u_in's value), stage 2 = J of
@@ -1287,33 +1301,7 @@ extern "C" int examg_jacobi2_boxes(const examg_layout_t *lu, const double *u_in,
                                    const examg_layout_t *lf, const double *rhs, const examg_stencil_t *st, double w,
                                    const int32_t *begin1, const int32_t *end1, const int32_t *begin2, const int32_t *end2,
                                    examg_stream_t stream) {
-  if (!lu || !u_in || !u_out || !lf || !rhs || !st || !begin1 || !end1 || !begin2 || !end2) { set_error("examg_jacobi2_boxes: null argument"); return 1; }
-  if (u_in == u_out) { set_error("examg_jacobi2_boxes: out of place only"); return 1; }
-  const Box box1 = make_box(begin1, end1), box2 = make_box(begin2, end2);
-  if (box2.count() == 0) return 0;
-  if (box2.b0 < box1.b0 || box2.b1 < box1.b1 || box2.b2 < box1.b2 || box2.e0 > box1.e0 || box2.e1 > box1.e1 || box2.e2 > box1.e2) {
-    set_error("examg_jacobi2_boxes: the stage-2 box must lie inside the stage-1 box");
-    return 1;
-  }
-  if (two_stage_ok(lu, lf, st, box2) && box_inside(lu, box1, 1) && box_inside(lf, box1, 0) && stage_boxes_ok(lf, box1, box2))
-    return launch_two_stage<false>(lu, u_in, lf, rhs, u_out, st, w, 0, box2, (hipStream_t)stream, &box1);
-  if (box1.b0 == box2.b0 && box1.b1 == box2.b1 && box1.b2 == box2.b2 && box1.e0 == box2.e0 && box1.e1 == box2.e1 && box1.e2 == box2.e2 &&
-      small_two_stage_ok(lu, lf, st, box2))
-    return launch_small_two_stage(false, 0, lu, u_in, u_out, lf, rhs, st, w, 0, box2, nullptr, nullptr, (hipStream_t)stream);
-  if (const int r27 = sf27_jacobi2_try(lu, u_in, u_out, lf, rhs, st, w, box1, box2, (hipStream_t)stream)) return r27 < 0 ? 1 : 0;
-  if (!tmp || tmp == u_in || tmp == u_out) { set_error("examg_jacobi2_boxes: fallback needs a distinct tmp array"); return 1; }
-  const int reach = stencil_reach(st);
-  int32_t b2[3], e2[3];
-  for (int d = 0; d < 3; ++d) {
-    const bool on = d < lu->nd;
-    b2[d] = begin1[d] - (on ? reach : 0);
-    e2[d] = end1[d] + (on ? reach : 0);
-  }
-  int rc = examg_axpby(lu, u_in, lu, tmp, 1.0, 0.0, b2, e2, stream);
-  if (rc) return rc;
-  rc = examg_jacobi(lu, u_in, tmp, lf, rhs, st, w, begin1, end1, stream);
-  if (rc) return rc;
-  return examg_jacobi(lu, tmp, u_out, lf, rhs, st, w, begin2, end2, stream);
+  return jacobi2_boxes("examg_jacobi2_boxes", lu, u_in, u_out, tmp, lf, rhs, st, w, begin1, end1, begin2, end2, stream);
 }
 
 // `u += Prolongation * uc` on [begin,end) followed by two Jacobi steps on the same box: u_out receives the result on the box,
@@ -1322,39 +1310,22 @@ extern "C" int examg_jacobi2_prolong(const examg_layout_t *lu, const double *u_i
                                      const examg_layout_t *lf, const double *rhs, const examg_stencil_t *st, double w,
                                      const int32_t *begin, const int32_t *end, const examg_layout_t *lc, const double *uc,
                                      examg_stream_t stream) {
-  if (!lu || !u_in || !u_out || !lf || !rhs || !st || !begin || !end || !lc || !uc) { set_error("examg_jacobi2_prolong: null argument"); return 1; }
-  if (u_in == u_out) { set_error("examg_jacobi2_prolong: out of place only"); return 1; }
+  const char *who = "examg_jacobi2_prolong";
+  if (!args_ok(who, lu && u_in && u_out && lf && rhs && st && begin && end && lc && uc, u_in, u_out, 0)) return 1;
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
-  if (two_stage_ok(lu, lf, st, box)) {
-    if (!prolong_args_ok("examg_jacobi2_prolong", lc, box)) return 1;
-    TSProl pr;
-    pr.lc = make_layout(lc);
-    pr.uc = uc;
-    return launch_two_stage<false>(lu, u_in, lf, rhs, u_out, st, w, 0, box, (hipStream_t)stream, nullptr, &pr);
-  }
-  if (small_two_stage_ok(lu, lf, st, box)) {
-    if (!prolong_args_ok("examg_jacobi2_prolong", lc, box)) return 1;
-    return launch_small_two_stage(false, 1, lu, u_in, u_out, lf, rhs, st, w, 0, box, lc, uc, (hipStream_t)stream);
-  }
-  if (!tmp || tmp == u_in || tmp == u_out) { set_error("examg_jacobi2_prolong: fallback needs a distinct tmp array"); return 1; }
-  const int reach = stencil_reach(st);
-  int32_t b2[3], e2[3];
-  for (int d = 0; d < 3; ++d) {
-    const bool on = d < lu->nd;
-    b2[d] = begin[d] - (on ? reach : 0);
-    e2[d] = end[d] + (on ? reach : 0);
-  }
+  if (const Route r = two_stage_route(lu, lf, st, box, box))
+    return launch_route<false>(r, who, lu, u_in, u_out, lf, rhs, st, w, 0, box, box, 1, lc, uc, (hipStream_t)stream);
+  if (!tmp_ok(who, tmp, u_in, u_out)) return 1;
+  int32_t gb[3], ge[3];
+  grow_box(begin, end, stencil_reach(st), lu->nd, gb, ge);
   // u_out holds the corrected field for the first step, tmp (with the box's shell) the intermediate one
-  int rc = examg_axpby(lu, u_in, lu, u_out, 1.0, 0.0, b2, e2, stream);
-  if (rc) return rc;
-  rc = examg_axpby(lu, u_in, lu, tmp, 1.0, 0.0, b2, e2, stream);
-  if (rc) return rc;
-  rc = examg_prolong_add(lc, uc, lu, u_out, begin, end, stream);
-  if (rc) return rc;
-  rc = examg_jacobi(lu, u_out, tmp, lf, rhs, st, w, begin, end, stream);
-  if (rc) return rc;
-  return examg_jacobi(lu, tmp, u_out, lf, rhs, st, w, begin, end, stream);
+  int rc = examg_axpby(lu, u_in, lu, u_out, 1.0, 0.0, gb, ge, stream);
+  if (!rc) rc = examg_axpby(lu, u_in, lu, tmp, 1.0, 0.0, gb, ge, stream);
+  if (!rc) rc = examg_prolong_add(lc, uc, lu, u_out, begin, end, stream);
+  if (!rc) rc = examg_jacobi(lu, u_out, tmp, lf, rhs, st, w, begin, end, stream);
+  if (!rc) rc = examg_jacobi(lu, tmp, u_out, lf, rhs, st, w, begin, end, stream);
+  return rc;
 }
 
 // Two Jacobi steps, u_in -> (u_in's values after two sweeps) in u_out; `tmp` is only used by the fallback
@@ -1362,27 +1333,7 @@ extern "C" int examg_jacobi2_prolong(const examg_layout_t *lu, const double *u_i
 extern "C" int examg_jacobi2(const examg_layout_t *lu, const double *u_in, double *u_out, double *tmp,
                              const examg_layout_t *lf, const double *rhs, const examg_stencil_t *st, double w,
                              const int32_t *begin, const int32_t *end, examg_stream_t stream) {
-  if (!lu || !u_in || !u_out || !lf || !rhs || !st || !begin || !end) { set_error("examg_jacobi2: null argument"); return 1; }
-  if (u_in == u_out) { set_error("examg_jacobi2: out of place only"); return 1; }
-  const Box box = make_box(begin, end);
-  if (box.count() == 0) return 0;
-  if (two_stage_ok(lu, lf, st, box)) return launch_two_stage<false>(lu, u_in, lf, rhs, u_out, st, w, 0, box, (hipStream_t)stream);
-  if (small_two_stage_ok(lu, lf, st, box)) return launch_small_two_stage(false, 0, lu, u_in, u_out, lf, rhs, st, w, 0, box, nullptr, nullptr, (hipStream_t)stream);
-  if (const int r27 = sf27_jacobi2_try(lu, u_in, u_out, lf, rhs, st, w, box, box, (hipStream_t)stream)) return r27 < 0 ? 1 : 0;
-  if (!tmp || tmp == u_in || tmp == u_out) { set_error("examg_jacobi2: fallback needs a distinct tmp array"); return 1; }
-  // the intermediate sweep needs the box's shell (Dirichlet / halo values) in tmp
-  const int reach = stencil_reach(st);
-  int32_t b2[3], e2[3];
-  for (int d = 0; d < 3; ++d) {
-    const bool on = d < lu->nd;
-    b2[d] = begin[d] - (on ? reach : 0);
-    e2[d] = end[d] + (on ? reach : 0);
-  }
-  int rc = examg_axpby(lu, u_in, lu, tmp, 1.0, 0.0, b2, e2, stream);
-  if (rc) return rc;
-  rc = examg_jacobi(lu, u_in, tmp, lf, rhs, st, w, begin, end, stream);
-  if (rc) return rc;
-  return examg_jacobi(lu, tmp, u_out, lf, rhs, st, w, begin, end, stream);
+  return jacobi2_boxes("examg_jacobi2", lu, u_in, u_out, tmp, lf, rhs, st, w, begin, end, begin, end, stream);
 }
 
 // Three Jacobi steps, u_in -> u_out on the box; one pass where k_three_stage7_lds applies (nothing outside the box is written), otherwise
@@ -1391,33 +1342,24 @@ extern "C" int examg_jacobi2(const examg_layout_t *lu, const double *u_in, doubl
 extern "C" int examg_jacobi3(const examg_layout_t *lu, const double *u_in, double *u_out, double *tmp, const examg_layout_t *lf,
                              const double *rhs, const examg_stencil_t *st, double w, const int32_t *begin, const int32_t *end,
                              examg_stream_t stream) {
-  if (!lu || !u_in || !u_out || !lf || !rhs || !st || !begin || !end) { set_error("examg_jacobi3: null argument"); return 1; }
-  if (u_in == u_out) { set_error("examg_jacobi3: out of place only"); return 1; }
+  const char *who = "examg_jacobi3";
+  if (!args_ok(who, lu && u_in && u_out && lf && rhs && st && begin && end, u_in, u_out, 0)) return 1;
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   if (three_stage_ok(lu, lf, st, box)) return launch_three_stage(lu, u_in, lf, rhs, u_out, st, w, box, (hipStream_t)stream);
-  if (!tmp || tmp == u_in || tmp == u_out) { set_error("examg_jacobi3: fallback needs a distinct tmp array"); return 1; }
-  const int reach = stencil_reach(st);
-  int32_t b2[3], e2[3];
-  for (int d = 0; d < 3; ++d) {
-    const bool on = d < lu->nd;
-    b2[d] = begin[d] - (on ? reach : 0);
-    e2[d] = end[d] + (on ? reach : 0);
-  }
-  // the first step into tmp (with the box's shell: Dirichlet / halo values for the steps behind it)
-  int rc = examg_axpby(lu, u_in, lu, tmp, 1.0, 0.0, b2, e2, stream);
+  if (!tmp_ok(who, tmp, u_in, u_out)) return 1;
+  // the first step into tmp (with the box's shell)
+  int rc = jacobi_through_tmp(lu, u_in, nullptr, tmp, lf, rhs, st, w, begin, end, nullptr, nullptr, stream);
   if (rc) return rc;
-  rc = examg_jacobi(lu, u_in, tmp, lf, rhs, st, w, begin, end, stream);
-  if (rc) return rc;
-  if (examg_two_stage_eligible(lu, lf, st, begin, end, begin, end))      // the pair in one pass (it does not touch its tmp then)
+  if (two_stage_route(lu, lf, st, box, box))      // the pair in one pass (it does not touch its tmp then)
     return examg_jacobi2(lu, tmp, u_out, nullptr, lf, rhs, st, w, begin, end, stream);
-  rc = examg_axpby(lu, u_in, lu, u_out, 1.0, 0.0, b2, e2, stream);
-  if (rc) return rc;
-  rc = examg_jacobi(lu, tmp, u_out, lf, rhs, st, w, begin, end, stream);       // second step: tmp -> u_out
-  if (rc) return rc;
-  rc = examg_jacobi(lu, u_out, tmp, lf, rhs, st, w, begin, end, stream);       // third step: u_out -> tmp
-  if (rc) return rc;
-  return examg_axpby(lu, tmp, lu, u_out, 1.0, 0.0, begin, end, stream);
+  int32_t gb[3], ge[3];
+  grow_box(begin, end, stencil_reach(st), lu->nd, gb, ge);
+  rc = examg_axpby(lu, u_in, lu, u_out, 1.0, 0.0, gb, ge, stream);
+  if (!rc) rc = examg_jacobi(lu, tmp, u_out, lf, rhs, st, w, begin, end, stream);       // second step: tmp -> u_out
+  if (!rc) rc = examg_jacobi(lu, u_out, tmp, lf, rhs, st, w, begin, end, stream);       // third step: u_out -> tmp
+  if (!rc) rc = examg_axpby(lu, tmp, lu, u_out, 1.0, 0.0, begin, end, stream);
+  return rc;
 }
 
 // 1 if examg_jacobi3 / examg_rbgs_colours3 will run their one-pass kernel for this box, 0 if they will run their loops one after the other
@@ -1434,20 +1376,9 @@ extern "C" int examg_three_stage_eligible(const examg_layout_t *lu, const examg_
 extern "C" int examg_rbgs_colours3(const examg_layout_t *lu, const double *u_in, double *u_out, const examg_layout_t *lf, const double *rhs,
                                    const examg_stencil_t *st, double w, int first, const int32_t *begin, const int32_t *end,
                                    examg_stream_t stream) {
-  if (!lu || !u_in || !u_out || !lf || !rhs || !st || !begin || !end) { set_error("examg_rbgs_colours3: null argument"); return 1; }
-  if (u_in == u_out) { set_error("examg_rbgs_colours3: out of place only"); return 1; }
-  if (first != 0 && first != 1) { set_error("examg_rbgs_colours3: first colour must be 0 or 1"); return 1; }
+  if (!args_ok("examg_rbgs_colours3", lu && u_in && u_out && lf && rhs && st && begin && end, u_in, u_out, first)) return 1;
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   if (three_stage_ok(lu, lf, st, box)) return launch_three_colours(lu, u_in, lf, rhs, u_out, st, w, first, box, (hipStream_t)stream);
-  const int reach = stencil_reach(st);
-  int32_t b2[3], e2[3];
-  for (int d = 0; d < 3; ++d) {
-    const bool on = d < lu->nd;
-    b2[d] = begin[d] - (on ? reach : 0);
-    e2[d] = end[d] + (on ? reach : 0);
-  }
-  int rc = examg_axpby(lu, u_in, lu, u_out, 1.0, 0.0, b2, e2, stream);
-  for (int k = 0; k < 3 && !rc; ++k) rc = examg_rbgs_colour(lu, u_out, lf, rhs, st, w, (k & 1) ? 1 - first : first, begin, end, stream);
-  return rc;
+  return colour_loops_on_copy(lu, u_in, u_out, nullptr, nullptr, lf, rhs, st, w, first, 3, begin, end, stream);
 }

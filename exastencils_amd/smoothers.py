@@ -152,8 +152,8 @@ def jacobi_pair(ops, comm, domain, S, F, A, w: float, tmp_field, overlap: bool =
 
     # The fallback of examg_jacobi2_boxes (short rows on coarse levels, other stencils) uses tmp as scratch for its whole
     # first step: it must then finish before the shell work writes tmp -- sequential order, no overlap.
-    # The kernel layer decides (ONE place: examg_two_stage_eligible -- stencil kind AND entry order, row length, box inside the
-    # allocation): only then may the shell work on tmp run concurrently on the side stream.
+    # The kernel layer decides (examg_two_stage_eligible, the route function the entry point itself switches on -- stencil kind AND
+    # entry order, row length, box inside the allocation): only then may the shell work on tmp run concurrently on the side stream.
     b1, e1 = shrunk(1)
     b2, e2 = shrunk(2)
     fused = hasattr(ops, "two_stage_eligible") and all(e2[d] > b2[d] for d in range(nd)) and \

@@ -67,6 +67,7 @@ class _Program:
         self.err_history: List[float] = []
         self.cg_iters: List[int] = []
         self._graphs: Dict = {}
+        self._one_pass: Dict[int, bool] = {}
 
     # `loop over <field>` bounds
     def bounds(self, f: Field, reduction: bool = False):
@@ -98,6 +99,15 @@ class _Program:
     def _single_block(self) -> bool:
         """No neighbour across any face (a periodic dimension makes a lone block its own neighbour: the paths with exchanges)."""
         return self.domain.world_size == 1 and not any(self.domain.periodic)
+
+    def _one_pass_sweep(self, l: int) -> bool:
+        """Does the kernel layer run the red-black sweep of level l as one pass (examg_two_stage_eligible)?"""
+        if l not in self._one_pass:
+            S = self.Solution[l]
+            b, e = self.bounds(S)
+            self._one_pass[l] = not hasattr(self.ops, "two_stage_eligible") or \
+                self.ops.two_stage_eligible(S.lc, self.RHS[l].lc, self.Laplace[l], b, e, b, e)
+        return self._one_pass[l]
 
     def _report_cg_limit(self):
         """One-call coarse solves count on the device how often the CG loop ran out of iterations (info[3]); the message the generated
@@ -387,17 +397,6 @@ class SolverFromL4(_Program):
         return curIt
 
     # repeat 3 times { color with { (i0+i1+i2) % 2, communicate; loop over Solution {...}; apply bc } }  (:204-213)
-    def _one_pass_sweep(self, l: int) -> bool:
-        """Does the kernel layer run the red-black sweep of level l as one pass (examg_two_stage_eligible)?"""
-        if not hasattr(self, "_one_pass"):
-            self._one_pass = {}
-        if l not in self._one_pass:
-            S = self.Solution[l]
-            b, e = self.bounds(S)
-            self._one_pass[l] = not hasattr(self.ops, "two_stage_eligible") or \
-                self.ops.two_stage_eligible(S.lc, self.RHS[l].lc, self.Laplace[l], b, e, b, e)
-        return self._one_pass[l]
-
     def _starts_from_zero(self, l: int) -> bool:
         """Is `Solution@l = 0` (in mgCycle@(l+1)) left to the first pre-smoothing sweep of level l?"""
         cfg = self.cfg
@@ -788,7 +787,7 @@ class SolverFromL3(_Program):
                     del cf
         nc = dom.ncells(lo)
         self._func_dir: Dict[int, bool] = {}       # level -> its boundary planes hold SetFuncDir's values (FMG start), not the field's bc
-        self._rb_alt, self._rb_tmp, self._one_pass = {}, {}, {}
+        self._rb_alt, self._rb_tmp = {}, {}
         self._cg_info = ops.new_array(4)
         self.VecP = Field("VecP", lo, FieldLayout.node(nd, nc, 1, True, True, cfg.align), ops, 1, FN_ZERO)
         self.VecGradP = Field("VecGradP", lo, FieldLayout.node(nd, nc, 0, False, False, cfg.align), ops, 1, None)
@@ -834,13 +833,7 @@ class SolverFromL3(_Program):
 
     # Function Smoother@((coarsest + 1) to finest)
     def _one_pass_sweep(self, l: int) -> bool:
-        """Does the kernel layer run the red-black sweep of level l as one pass (examg_two_stage_eligible)?"""
-        if l not in self._one_pass:
-            S = self.Solution[l]
-            b, e = self.bounds(S)
-            self._one_pass[l] = self.nd == 3 and (not hasattr(self.ops, "two_stage_eligible") or
-                                                  self.ops.two_stage_eligible(S.lc, self.RHS[l].lc, self.Laplace[l], b, e, b, e))
-        return self._one_pass[l]
+        return self.nd == 3 and super()._one_pass_sweep(l)      # this program's one-pass forms are 3-D only: 2-D does not ask
 
     def _sweep_arrays(self, l: int):
         """Second Solution array of the out-of-place red-black sweeps (+ the scratch field of the shell on blocks with neighbours)."""

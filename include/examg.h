@@ -234,7 +234,10 @@ int examg_jacobi2_prolong(const examg_layout_t *lu, const double *u_in, double *
 
 /* 1 if examg_jacobi2_boxes / examg_rbgs_sweep_fused_boxes will run their one-pass kernel for these arguments, 0 if they will
  * take the fallback that writes `tmp` on the launch stream (other stencils or entry orders, short rows, boxes at the edge of
- * the allocation).  A caller that overlaps the pass with work on `tmp` on another stream must ask here first. */
+ * the allocation, planes of 2^32 elements or more).  A caller that overlaps the pass with work on `tmp` on another stream, or that
+ * passes no `tmp`, must ask here first.  The entry points take their route from the function that answers here: where the answer
+ * is 1 they neither read nor write `tmp`.  (Where it is 0, examg_jacobi2 / examg_jacobi2_boxes may still run 27-entry record
+ * fields in one pass.) */
 int examg_two_stage_eligible(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const int32_t *begin1,
                              const int32_t *end1, const int32_t *begin2, const int32_t *end2);
 

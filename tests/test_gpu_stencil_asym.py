@@ -308,6 +308,66 @@ def test_one_pass_sweeps(hip, orc, ex, case, kind, data):
     _sweep_case(hip, orc, ex, case, kind, data, first=1 if "rbgs" in kind and case[1] == "align16" else 0)
 
 
+SENTINEL = -12345.678
+
+
+def _two_box_run(gpu, kind, lu, lf, st, w, boxes, tmp):
+    """examg_rbgs_sweep_fused_boxes / examg_jacobi2_boxes / examg_jacobi2 (boxes = (b, e) only) on random data; tmp: an array or None."""
+    u, f, out = fields(gpu, "random", (lu, lf, lu), 400)
+    L, F = lu.c_struct(), lf.c_struct()
+    if kind == "rbgs_boxes":
+        gpu.rbgs_sweep_fused_boxes(L, u, out, tmp, F, f, st, w, 1, *boxes)
+    elif kind == "jacobi2_boxes":
+        gpu.jacobi2_boxes(L, u, out, tmp, F, f, st, w, *boxes)
+    else:
+        gpu.jacobi2(L, u, out, tmp, F, f, st, w, *boxes)
+    return host(gpu, [out, u, f])
+
+
+@pytest.mark.parametrize("shrunk", [False, True], ids=["equal", "shrunk"])
+@pytest.mark.parametrize("kind", ["rbgs_boxes", "jacobi2_boxes"])
+@pytest.mark.parametrize("case", SWEEP_CASES, ids=SWEEP_IDS)
+def test_two_box_forms_do_what_the_query_promises(hip, case, kind, shrunk):
+    """examg_two_stage_eligible against the two-box entry points (callers pass tmp = NULL on the strength of its answer): where it
+    answers 1 the call succeeds without a tmp, gives the bits of the call with one and leaves a tmp that is passed untouched over the
+    whole array; where it answers 0 the call without a tmp is the 'needs a distinct tmp' error (examg_jacobi2_boxes: unless the stencil
+    is a 27-entry record field, which the record pair may still run in one pass)."""
+    from exastencils_amd.lib import ExamgError
+
+    shape, lay, which, skind, order, _ = case
+    lu, lf = layouts(3, shape, lay)
+    b, e = box(3, shape, which)
+    st = stencil(skind, order, "random", shape)
+    w = weight(st, "random")
+    boxes = (b, e) + (tuple(_boxes2(b, e, 3)) if shrunk else (b, e))
+    if hip.two_stage_eligible(lu.c_struct(), lf.c_struct(), st, *boxes):
+        tmp = hip.from_host(np.full(lu.size, SENTINEL))
+        with_tmp = _two_box_run(hip, kind, lu, lf, st, w, boxes, tmp)
+        assert_same(_two_box_run(hip, kind, lu, lf, st, w, boxes, None), with_tmp, "%s without tmp" % kind)
+        assert np.array_equal(host(hip, [tmp])[0], np.full(lu.size, SENTINEL)), "%s wrote its tmp on the one-pass route" % kind
+    elif kind == "rbgs_boxes" or not (st.cfield is not None and len(st.offsets) == 27):
+        with pytest.raises(ExamgError, match="needs a distinct tmp"):
+            _two_box_run(hip, kind, lu, lf, st, w, boxes, None)
+
+
+def test_jacobi2_is_jacobi2_boxes_with_equal_boxes(hip):
+    """examg_jacobi2 against examg_jacobi2_boxes with box 2 = box 1 on a one-pass case and on a fallback case: u_out, the inputs and
+    tmp over the whole arrays."""
+    for case in (SWEEP_CASES[0], SWEEP_CASES[8]):
+        shape, lay, which, skind, order, path = case
+        lu, lf = layouts(3, shape, lay)
+        b, e = box(3, shape, which)
+        st = stencil(skind, order, "random", shape)
+        w = weight(st, "random")
+        assert hip.two_stage_eligible(lu.c_struct(), lf.c_struct(), st, b, e, b, e) == (path != "fallback")
+        got = []
+        for kind, boxes in (("jacobi2", (b, e)), ("jacobi2_boxes", (b, e, b, e))):
+            tmp = hip.from_host(np.full(lu.size, SENTINEL))
+            got.append(_two_box_run(hip, kind, lu, lf, st, w, boxes, tmp) + host(hip, [tmp]))
+        assert_same(got[0], got[1], "jacobi2 against jacobi2_boxes, %s" % path)
+        assert np.array_equal(got[0][3], np.full(lu.size, SENTINEL)) == (path != "fallback")
+
+
 @pytest.mark.parametrize("data", DATA)
 @pytest.mark.parametrize("kind", ["rbgs", "jacobi2", "rbgs_prolong", "jacobi2_boxes"])
 def test_two_stage_workgroup_shapes(orc, ex, two_stage_variant, kind, data):

@@ -59,7 +59,7 @@ from .domain import RectDomain
 from .field import Field, Stencil
 from .layout import FieldLayout
 from .exa4_parser import (Exa4SyntaxError, Exa4Unsupported, FunctionDecl, Parser, _COORD, _GRIDW, _MATH, _arith,  # noqa: F401
-                          _colour_cond, _conjuncts, _const_value, _contains, _find_calls, _has_coord, _lower_cond, _parity_expr, _walk)
+                          _colour_cond, _colour_expr, _conjuncts, _const_value, _contains, _find_calls, _has_coord, _lower_cond, _parity_expr, _walk)
 
 from .exa4_common import (APPLY, RESIDUAL, SMOOTH, _FN_2D_ONLY, _FN_ANY_DIM, _FN_WITH_PARAM, _N_FN, _Frame, _Return, fn_eval)  # noqa: E402,F401
 from .exa4_builtins import Builtins  # noqa: E402
@@ -896,11 +896,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
         elif k == "if":
             self._exec_block(s[2] if self._eval(s[1], fr) else s[3], fr)
         elif k == "color":
-            if len(s[1]) != 1:
-                raise Exa4Unsupported("color with more than one colour expression")
-            shift = _parity_expr(s[1][0], self.nd)
+            shift = _parity_expr(s[1][0], self.nd) if len(s[1]) == 1 else None
             if shift is None:
-                raise Exa4Unsupported("colour expression other than (i0 + i1 [+ i2]) % 2")
+                return self._exec_multicolour(s, fr)
             if self.fuse and self._try_fused_sweep(s[2], (0 - shift) % 2, fr):
                 return
             saved = fr.colour
@@ -915,6 +913,102 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
             raise _Return(self._eval(s[1], fr) if s[1] is not None else None)
         else:
             raise Exa4SyntaxError("statement %r" % (k,))
+
+    def _exec_multicolour(self, s, fr: _Frame):
+        """`color with { e_0 [, e_1 [, e_2]], <statements> }` with anything but the one parity expression of all indices
+        (baseExt/l4/L4_ColorLoops.scala:32-66): the statements run once per element of the cross product of the remainders, the
+        first expression varying fastest; loops inside take the points of the current colour (examg_stencil_op_coloured)."""
+        from .field import Colouring
+
+        if len(s[1]) > 3:
+            raise Exa4Unsupported("color with more than three colour expressions")
+        exprs = []
+        for e in s[1]:
+            ce = _colour_expr(e, self.nd)
+            if ce is None:
+                raise Exa4Unsupported("colour expression other than (s + i_a [+ i_b [+ i_c]]) % n with a positive integer n")
+            exprs.append(ce)
+        if fr.colour is not None or fr.mcolour is not None:
+            raise Exa4Unsupported("color with inside color with")
+        col = Colouring(tuple(exprs))
+        if self.fuse and self._try_mcgs_sweep(s[2], col, fr):
+            return
+        try:
+            for c in col.colours():
+                fr.mcolour = c
+                self._exec_block(s[2], fr)
+        finally:
+            fr.mcolour = None
+
+    def _exec_loop_multicolour(self, s, fr: _Frame):
+        """A `loop over` inside a multi-colouring: the stencil loops (A * u, f - A * u, the damped-residual update) on the points of
+        the current colour.  Everything else has no coloured kernel and is refused by name."""
+        _, target, only, where, reduction, body = s
+        f, _ = self._field(target, fr)
+        if f.layout.is_cell or self._touches_cell(body):
+            raise Exa4Unsupported("cell fields in a loop under a multi-colouring (color with several expressions)")
+        if reduction is not None:
+            raise Exa4Unsupported("reduction loop under a multi-colouring (color with several expressions)")
+        if only is not None or fr.contract is not None:
+            raise Exa4Unsupported("loop ... only <region> / contraction under a multi-colouring (color with several expressions)")
+        if where is not None and any(_colour_cond(c, self.nd) is not None for c in _conjuncts(where)):
+            raise Exa4Unsupported("`where` colour test in a loop under a multi-colouring (color with several expressions)")
+        boxes, _ = self._loop_boxes(f, only, where, reduction, fr)
+        for st in body:
+            if st[0] != "assign":
+                raise Exa4Unsupported("statement %r inside a loop body" % st[0])
+            for b, e in boxes:
+                self._exec_point_assign_multicolour(st, b, e, fr)
+
+    def _exec_point_assign_multicolour(self, st, b, e, fr: _Frame):
+        op, lhs, rhs = st[1], st[2], st[3]
+        col = fr.mcolour
+        what = "under a multi-colouring (color with several expressions)"
+        if lhs[0] != "fld":
+            raise Exa4Unsupported("loop body assigns to %s" % lhs[0])
+        D, ds = self._field(lhs, fr)
+
+        def plain(*fields):
+            for X in fields:
+                if X.layout.transform:
+                    raise Exa4Unsupported("colour-split field %s %s" % (X.name, what))
+
+        def in_place_ok(kind, U, us, A):
+            # a loop that reads the array it writes: only where no point of the colour is a neighbour of another one
+            if D is U and ds == us and not col.decouples(A.offsets):
+                raise Exa4Unsupported("in-place %s %s: the colouring does not decouple the stencil (two points of one colour are "
+                                      "neighbours: the generated loop depends on its order)" % (kind, what))
+
+        m = self._match_smoother(st, fr) if op in ("=", "+=") else None
+        if m is None and op in ("=", "+="):
+            # _match_smoother declines fields under a layout transformation: name the construct instead of "not a kernel"
+            for n in _walk(st):
+                if n and n[0] == "fld" and isinstance(n[1], str) and self._field(n, fr)[0].layout.transform:
+                    raise Exa4Unsupported("colour-split field %s %s" % (n[1], what))
+        if m is not None:
+            D, ds, U, us, F, fs, A, wv = m
+            plain(D, U, F)
+            in_place_ok("smoother", U, us, A)
+            self.launches += 1
+            return self.ops.stencil_op_coloured(SMOOTH, U.lc, U.data(us), F.lc, F.data(fs), D.lc, D.data(ds), A, wv, col, b, e)
+        if op == "=":
+            r = self._residual_form(rhs, fr)
+            if r is not None:
+                F, fs = self._field(r[0], fr)
+                U, us = self._field(r[2], fr)
+                plain(D, U, F)
+                in_place_ok("residual loop", U, us, r[1])
+                self.launches += 1
+                return self.ops.stencil_op_coloured(RESIDUAL, U.lc, U.data(us), F.lc, F.data(fs), D.lc, D.data(ds), r[1], 0.0, col, b, e)
+            a = self._sten_times_field(rhs, fr)
+            if a is not None and a[1] == "stencil" and a[0] == 1.0:
+                X, xs = self._field(a[4], fr)
+                plain(D, X)
+                in_place_ok("stencil application", X, xs, a[2])
+                self.launches += 1
+                return self.ops.stencil_op_coloured(APPLY, X.lc, X.data(xs), None, None, D.lc, D.data(ds), a[2], 0.0, col, b, e)
+        raise Exa4Unsupported("loop body statement %s %s ... %s: only stencil loops (A * u, f - A * u, u + w * (f - A * u)) have a coloured kernel"
+                              % (lhs[1], op, what))
 
     def _apply_bc(self, f: Field, slot: int):
         if f.layout.is_cell:
@@ -1012,6 +1106,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
             raise Exa4Unsupported("loop over node field %s with a body over cell fields" % f.name)
         if f.layout.is_cell and (only is not None or fr.contract is not None):
             raise Exa4Unsupported("loop over cell field %s: `only` regions and contraction" % f.name)
+        if fr.mcolour is not None:
+            return self._exec_loop_multicolour(s, fr)
         boxes, colour = self._loop_boxes(f, only, where, reduction, fr)
         if reduction is not None:
             return self._exec_reduction(f, boxes, reduction, body, fr)

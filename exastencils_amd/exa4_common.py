@@ -83,4 +83,5 @@ class _Frame:
     level: Optional[int]
     vars: Dict[str, object]
     colour: Optional[int] = None
+    mcolour: Optional[object] = None     # inside `color with` of a multi-colouring: the Colouring with the remainders of the current colour
     contract: Optional[tuple] = None     # (extent, posExt, negExt) inside `repeat .. with contraction`: loops widen at interior faces

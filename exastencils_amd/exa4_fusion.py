@@ -157,7 +157,7 @@ class LazyFusions:
     def _consume_residual(self, s, fr) -> bool:
         P = self._pending
         _, target, only, where, reduction, body = s
-        if only is not None or where is not None or fr.colour is not None or fr.contract is not None or len(body) != 1:
+        if only is not None or where is not None or fr.colour is not None or fr.mcolour is not None or fr.contract is not None or len(body) != 1:
             return False
         st = body[0]
         D, U, F, A = P["D"], P["U"], P["F"], P["A"]
@@ -209,14 +209,14 @@ class LazyFusions:
     def _dead_after(self, key: Tuple[str, int]) -> bool:
         may_return = False
         for body, idx, fr, is_loop, is_fn in reversed(self._cont):
-            st, ret = self._scan(body[idx + 1:], fr.level, key, fr.colour is not None)
+            st, ret = self._scan(body[idx + 1:], fr.level, key, fr.colour is not None or fr.mcolour is not None)
             if st == READ:
                 return False
             if st == WRITTEN and not (may_return or ret):
                 return True
             may_return = may_return or ret
             if is_loop:                       # the body may run again from its start (and the loop may also end here)
-                st2, ret2 = self._scan(body[:idx + 1], fr.level, key, fr.colour is not None)
+                st2, ret2 = self._scan(body[:idx + 1], fr.level, key, fr.colour is not None or fr.mcolour is not None)
                 if st2 == READ:
                     return False
                 may_return = may_return or ret2

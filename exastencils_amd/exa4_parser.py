@@ -833,6 +833,37 @@ def _index_sum(e, nd: int):
     return None
 
 
+def _index_subset_sum(e):
+    """(constant c, axes) if e == c + a sum of distinct indices i_d (each at most once, at least one), else None."""
+    seen, const = [], 0
+
+    def rec(x):
+        nonlocal const
+        if x[0] == "bin" and x[1] == "+":
+            return rec(x[2]) and rec(x[3])
+        if x[0] == "id" and isinstance(x[1], str) and re.fullmatch(r"i[012]", x[1]):
+            seen.append(int(x[1][1]))
+            return True
+        if x[0] == "num" and isinstance(x[1], int):
+            const += x[1]
+            return True
+        return False
+
+    if rec(e) and seen and len(set(seen)) == len(seen):
+        return const, tuple(sorted(seen))
+    return None
+
+
+def _colour_expr(e, nd: int):
+    """(axes, shift, mod) if e == (shift + i_a [+ i_b [+ i_c]]) % mod with a positive integer constant mod and axes below nd -- a
+    colour expression of `color with` (baseExt/l4/L4_ColorLoops.scala:32-66) -- else None."""
+    if e[0] == "bin" and e[1] == "%" and e[3][0] == "num" and isinstance(e[3][1], int) and e[3][1] > 0:
+        m = _index_subset_sum(e[2])
+        if m is not None and all(d < nd for d in m[1]):
+            return m[1], m[0], e[3][1]
+    return None
+
+
 def _parity_expr(e, nd: int):
     """shift s if e == (s + i0 + i1 [+ i2]) % 2."""
     if e[0] == "bin" and e[1] == "%" and e[3] == ("num", 2):

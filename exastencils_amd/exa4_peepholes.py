@@ -121,6 +121,40 @@ class Peepholes:
         self._alt[key], U.slots[us] = U.slots[us], alt
         return True
 
+    def _try_mcgs_sweep(self, body, col, fr: _Frame) -> bool:
+        """`color with { e_0, e_1, .., [communicate u] loop over u { u += w (f - A u) } [apply bc to u] }` on one block: every
+        `communicate` is empty and `apply bc` re-writes position-only values no colour loop touches, so the whole statement is one
+        examg_mcgs_sweep -- the colour loops in the reference's order, in place; 27-entry record fields take two colours per launch."""
+        if self.domain.world_size != 1 or any(self.domain.periodic) or not hasattr(self.ops, "mcgs_sweep"):
+            return False
+        if self._touches_cell(body):
+            return False
+        # exactly `[communicate u] loop over u { .. } [apply bc to u]`, in this order
+        kinds = [st[0] for st in body]
+        if kinds not in (["loop"], ["comm", "loop"], ["loop", "applybc"], ["comm", "loop", "applybc"]):
+            return False
+        lp = body[kinds.index("loop")]
+        if lp[2] is not None or lp[3] is not None or lp[4] is not None or len(lp[5]) != 1 or fr.contract is not None:
+            return False
+        m = self._match_smoother(lp[5][0], fr)
+        if m is None:
+            return False
+        D, ds, U, us, F, fs, A, w = m
+        if D is not U or ds != us or not col.decouples(A.offsets):
+            return False        # the statement-by-statement path runs it, or names what it cannot run
+        if self._field(lp[1], fr)[0] is not U:
+            return False
+        for st in body:
+            if st[0] in ("comm", "applybc") and self._field(st[-1], fr) != (U, us):
+                return False    # another field, or another slot of u
+        if U.bc_fn is not None and (U.name, U.level, us) not in self._bc_valid:
+            return False        # boundary planes not known to hold the Dirichlet values yet: the plain path applies them
+        b, e = self.domain.loop_bounds(U.layout)
+        self.launches += 1
+        self.ops.mcgs_sweep(U.lc, U.data(us), F.lc, F.data(fs), A, w, col, b, e)
+        self.fusions["mcgs_sweep"] = self.fusions.get("mcgs_sweep", 0) + 1
+        return True
+
     def _try_jacobi_pairs(self, body, n: int, fr: _Frame) -> bool:
         """`repeat n times { Smoother ( ) }` with Smoother = [communicate ghost of u<active>; loop over u { u<next> =
         u<active> + w (f - A u<active>) }; advance u]: consecutive pairs as one pass over HBM (exastencils_amd/smoothers.py)."""

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field as _dc_field
 from typing import List, Optional, Sequence, Tuple
 
 from .layout import FieldLayout
-from .lib import StencilC
+from .lib import ColouringC, StencilC
 
 # Named point functions of the reference's programs (boundary values, right-hand sides, exact solutions, coefficient profiles).
 # They are HOST-side names only: the library knows expression programs (examg_expr_t) and nothing else -- FN_PROGRAMS below
@@ -121,6 +121,56 @@ class Stencil:
         else:
             s.cfield = None
         return s
+
+
+@dataclass(frozen=True)
+class Colouring:
+    """`color with { e_0, e_1, .. }` (baseExt/l4/L4_ColorLoops.scala:32-66): 1 to 3 expressions, each a tuple (axes, shift, mod) for
+    e = (shift + sum of i_d over the axes d) % mod, and -- for one colour -- the remainder of every expression (include/examg.h,
+    examg_colouring_t).  The body runs once per colour, the first expression varying fastest."""
+    exprs: Tuple[Tuple[Tuple[int, ...], int, int], ...]
+    rem: Tuple[int, ...] = ()
+
+    def __post_init__(self):
+        if not 1 <= len(self.exprs) <= 3:
+            raise ValueError("a colouring has 1 to 3 expressions")
+        for axes, shift, mod in self.exprs:
+            if not axes or len(set(axes)) != len(axes) or any(d not in (0, 1, 2) for d in axes) or int(mod) <= 0:
+                raise ValueError("colour expression (axes %r, shift %r, mod %r)" % (axes, shift, mod))
+        if self.rem and (len(self.rem) != len(self.exprs) or any(not 0 <= r < e[2] for r, e in zip(self.rem, self.exprs))):
+            raise ValueError("remainders %r of the colouring %r" % (self.rem, self.exprs))
+
+    @staticmethod
+    def axis_parity(nd: int) -> "Colouring":
+        """`i0 % 2, i1 % 2 [, i2 % 2]`: the 2^nd colours that decouple every stencil of reach 1."""
+        return Colouring(tuple(((d,), 0, 2) for d in range(nd)))
+
+    def colours(self):
+        """Every colour in the order of the reference's colour loops: the first expression varies fastest."""
+        import itertools
+
+        for r in itertools.product(*[range(e[2]) for e in reversed(self.exprs)]):
+            yield Colouring(self.exprs, tuple(reversed(r)))
+
+    def decouples(self, offsets) -> bool:
+        """Does every entry offset o != 0 change the value of some expression?  Only then is an in-place loop over one colour
+        independent of the loop order."""
+        return all(any(sum(o[d] for d in axes) % mod != 0 for axes, _, mod in self.exprs) for o in offsets if any(o))
+
+    def parity_colour(self, nd: int) -> Optional[int]:
+        """The colour of examg_stencil_op's own colouring, (i0 + i1 [+ i2]) % 2, if this is a colour of it; else None."""
+        if len(self.exprs) == 1 and self.rem and self.exprs[0][2] == 2 and sorted(self.exprs[0][0]) == list(range(nd)):
+            return (self.rem[0] - self.exprs[0][1]) % 2
+        return None
+
+    def c_struct(self) -> ColouringC:
+        c = ColouringC()
+        c.nexpr = len(self.exprs)
+        for k, (axes, shift, mod) in enumerate(self.exprs):
+            c.axes[k] = sum(1 << d for d in axes)
+            c.shift[k], c.mod[k] = int(shift), int(mod)
+            c.rem[k] = int(self.rem[k]) if self.rem else 0
+        return c
 
 
 def _axis(d: int, s: int) -> Tuple[int, int, int]:

@@ -36,6 +36,11 @@ class GeomC(C.Structure):
     _fields_ = [("pos_begin", C.c_double * 3), ("h", C.c_double * 3)]
 
 
+class ColouringC(C.Structure):
+    """examg_colouring_t: 1 to 3 colour expressions (shift + sum of the axes' indices) % mod and the remainders of one colour."""
+    _fields_ = [("nexpr", C.c_int32)] + [(n, C.c_int32 * 3) for n in ("axes", "shift", "mod", "rem")]
+
+
 MAX_EXPR = 256
 OPS = {"const": 0, "x": 1, "y": 2, "z": 3, "+": 4, "-": 5, "*": 6, "/": 7, "neg": 8, "sin": 9, "cos": 10, "exp": 11, "sinh": 12,
        "cosh": 13, "sqrt": 14, "pow": 15, "tan": 16, "log": 17, "fabs": 18, "max": 19, "min": 20, "tanh": 21}
@@ -82,6 +87,7 @@ SYMBOLS = [
     "examg_comm_peer_gather_bytes", "examg_comm_status",
     "examg_sum", "examg_add_scalar", "examg_fill_expr_cell", "examg_max_err_expr_cell", "examg_apply_bc_cell", "examg_restrict_cell",
     "examg_prolong_add_cell",
+    "examg_stencil_op_coloured", "examg_mcgs_sweep", "examg_mcgs_one_pass_eligible",
 ]
 
 COMM_ID_BYTES = 128
@@ -200,6 +206,10 @@ def load(path=None):
     L.examg_apply_bc_cell.argtypes = [lp, vp, gp, C.c_int, ep, C.c_uint32, vp]
     L.examg_restrict_cell.argtypes = [lp, vp, lp, vp, C.c_double, ip, ip, vp]
     L.examg_prolong_add_cell.argtypes = [lp, vp, lp, vp, ip, ip, vp]
+    cp = C.POINTER(ColouringC)
+    L.examg_stencil_op_coloured.argtypes = [C.c_int, lp, vp, lp, vp, lp, vp, sp, C.c_double, cp, ip, ip, vp]
+    L.examg_mcgs_sweep.argtypes = [lp, vp, lp, vp, sp, C.c_double, cp, ip, ip, vp]
+    L.examg_mcgs_one_pass_eligible.argtypes = [lp, lp, sp, cp, ip, ip]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("examg_version", "examg_last_error", "examg_device_count", "examg_reduce_work_bytes", "examg_exchange_workspace_bytes",
@@ -211,6 +221,9 @@ def load(path=None):
     if hasattr(L, "examg_debug_cell_narrow"):        # debug build only: the 8-byte form of the cell transfer kernels
         L.examg_debug_cell_narrow.argtypes = [C.c_int]
         L.examg_debug_cell_narrow.restype = C.c_int
+    if hasattr(L, "examg_debug_mcgs_per_colour"):    # debug build only: examg_mcgs_sweep as its colour loops
+        L.examg_debug_mcgs_per_colour.argtypes = [C.c_int]
+        L.examg_debug_mcgs_per_colour.restype = C.c_int
     _libs[path] = L
     if path == LIB_PATH:
         _lib = L

@@ -11,7 +11,7 @@ import ctypes as C
 from typing import Optional, Sequence
 
 from . import lib as _lib
-from .field import Stencil, fn_expr
+from .field import Colouring, Stencil, fn_expr  # noqa: F401  (Colouring: the value type of the coloured entry points)
 from .lib import ExamgError, check, ivec
 
 
@@ -69,6 +69,24 @@ class HipOps:
                                       self.ptr(rhs) if rhs is not None else None, C.byref(ld), self.ptr(dst),
                                       C.byref(sc), float(w), int(colour), ivec(begin), ivec(end), self._stream()),
               "examg_stencil_op")
+
+    def stencil_op_coloured(self, mode: int, lu, u, lf, rhs, ld, dst, st: Stencil, w: float, col: Colouring, begin, end):
+        """A stencil loop on the points of one colour of a multi-colouring (examg_stencil_op_coloured)."""
+        sc, cc = st.c_struct(self.ptr), col.c_struct()
+        check(self.L.examg_stencil_op_coloured(mode, C.byref(lu), self.ptr(u), C.byref(lf) if lf is not None else None,
+                                               self.ptr(rhs) if rhs is not None else None, C.byref(ld), self.ptr(dst), C.byref(sc), float(w),
+                                               C.byref(cc), ivec(begin), ivec(end), self._stream()), "examg_stencil_op_coloured")
+
+    def mcgs_sweep(self, lu, u, lf, rhs, st: Stencil, w: float, col: Colouring, begin, end):
+        """All colour loops of an in-place smoother on a block without neighbours, in the reference's order (examg_mcgs_sweep)."""
+        sc, cc = st.c_struct(self.ptr), col.c_struct()
+        check(self.L.examg_mcgs_sweep(C.byref(lu), self.ptr(u), C.byref(lf), self.ptr(rhs), C.byref(sc), float(w), C.byref(cc), ivec(begin),
+                                      ivec(end), self._stream()), "examg_mcgs_sweep")
+
+    def mcgs_one_pass_eligible(self, lu, lf, st: Stencil, col: Colouring, begin, end) -> bool:
+        """Will mcgs_sweep run its row-pair kernel (True) or the colour loops one by one?"""
+        sc, cc = st.c_struct(self.ptr), col.c_struct()
+        return bool(self.L.examg_mcgs_one_pass_eligible(C.byref(lu), C.byref(lf), C.byref(sc), C.byref(cc), ivec(begin), ivec(end)))
 
     def rbgs_sweep_fused(self, lu, u_in, u_out, lf, rhs, st: Stencil, w: float, first: int, begin, end):
         sc = st.c_struct(self.ptr)

@@ -708,10 +708,12 @@ class ConfigL3:
     min_level: int = 0
     max_level: int = 4
     frag_len: Tuple[int, int, int] = (1, 1, 1)
-    smoother: str = "jacobi"            # 'jacobi' (2 slots) | 'rbgs'
+    # 'jacobi' (2 slots) | 'rbgs' | 'mcgs': the 2^nd-colour Gauss-Seidel sweep `color with { i0 % 2, i1 % 2 [, i2 % 2], communicate
+    # Solution, loop over Solution { .. in place .. } }` -- what red-black is for star stencils, for stencils with diagonal neighbours
+    smoother: str = "jacobi"
     omega: float = 0.8
     n_smooth: int = 3
-    stencil: str = "unit"               # 'unit' | 'scaled' | 'varcoeff'
+    stencil: str = "unit"               # 'unit' | 'scaled' | 'varcoeff' | 'helmholtz27'
     restrict_scale: float = 4.0
     tol: float = 1.0e-5
     max_it: int = 100
@@ -750,6 +752,13 @@ class SolverFromL3(_Program):
         self.cfg = cfg
         nd, dom, ops = cfg.nd, self.domain, self.ops
         lo, hi = cfg.min_level, cfg.max_level
+        if cfg.smoother not in ("jacobi", "rbgs", "mcgs"):
+            raise ValueError("ConfigL3.smoother %r" % (cfg.smoother,))
+        if cfg.smoother == "mcgs":
+            # the one-pass forms of the other two smoothers have no multi-colour counterpart: asking for one is a mistake, not a no-op
+            fused = [n for n in ("temporal_blocking", "fused_rbgs", "fused_prolong_min_points", "fused_zero_start", "fused_smooth_residual")
+                     if getattr(cfg, n)]
+            assert not fused, "ConfigL3(smoother='mcgs') with %s: these options belong to the Jacobi / red-black smoothers" % ", ".join(fused)
         nslots = 2 if cfg.smoother == "jacobi" else 1
         prm = (cfg.kappa,)
         self.Solution: Dict[int, Field] = {}
@@ -885,6 +894,19 @@ class SolverFromL3(_Program):
 
             self.communicate(S, S.active, "dup")       # the ghost part of `communicate Solution` is inside rbgs_sweep
             self._rb_alt[l] = rbgs_sweep(self.ops, self.comm, self.domain, S, F, A, self._w(l), alt, self._rb_tmp[l], 0)
+        elif self.cfg.smoother == "mcgs":
+            # color with { i0 % 2, i1 % 2 [, i2 % 2], communicate Solution, loop over Solution { Solution += w * (RHS - A * Solution) } }
+            assert correction_from is None and not zero_input
+            from .field import Colouring
+
+            col = Colouring.axis_parity(self.nd)
+            if self._single_block():
+                # every `communicate` of the colour loops is empty: the whole sweep is one call (examg_mcgs_sweep)
+                self.ops.mcgs_sweep(S.lc, S.data(), F.lc, F.data(), A, self._w(l), col, b, e)
+            else:
+                for c in col.colours():
+                    self.communicate(S, S.active)
+                    self.ops.stencil_op_coloured(SMOOTH, S.lc, S.data(), F.lc, F.data(), S.lc, S.data(), A, self._w(l), c, b, e)
         else:                                   # Testing/Smoothers/RBGS.exa4:125-133
             assert correction_from is None and not zero_input
             for colour in (0, 1):

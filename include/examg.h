@@ -128,6 +128,57 @@ int examg_residual(const examg_layout_t *lu, const double *u, const examg_layout
                    const examg_layout_t *lr, double *res, const examg_stencil_t *st, const int32_t *begin,
                    const int32_t *end, examg_stream_t stream);
 
+/* ---- multi-colour loops: `color with { e_0, e_1, ... }` with more than one colour expression, or with an expression other than the
+ * parity of all indices (baseExt/l4/L4_ColorLoops.scala:32-66; Examples/Stokes/2D_FV_Stokes_fromL4.exa4:588-591 `i0 % 3, i1 % 3`).
+ * A COLOURING is a list of nexpr = 1 .. 3 expressions
+ *     e_k = (shift[k] + sum of i_d over the axes d with bit d of axes[k] set) % mod[k]
+ * mod[k] a positive constant, axes[k] a non-empty set of axes of the layout (bits below nd), shift[k] an integer constant, i_d the
+ * loop's iterator coordinates (fragment-local, 0 = lower duplicate node: the coordinates of `colour` above).  A COLOUR fixes a
+ * remainder rem[k] in [0, mod[k]) for every expression; a point belongs to it when every e_k == rem[k].
+ * Order of the colour loops (L4_ColorLoops.toRepeatLoops): the body runs once per element of the cross product of the remainders, the
+ * FIRST expression varying fastest: for `i0 % 2, i1 % 2, i2 % 2` the colours (0,0,0), (1,0,0), (0,1,0), (1,1,0), (0,0,1), ...
+ * A colouring DECOUPLES a stencil when every entry offset o != 0 has an expression k with (sum of o_d over the axes of e_k) mod mod[k]
+ * != 0: no point of a colour is then a neighbour of another point of that colour, and only then is an in-place loop over one colour
+ * independent of the loop order -- only then may u and dst alias.  `i0 % 2, i1 % 2, i2 % 2` decouples every stencil of reach 1 (the
+ * 8-colour Gauss-Seidel sweep of 27-point stencils: what red-black is for 7-point ones); the parity of all indices decouples star
+ * stencils only.
+ * The coloured entry points refuse a box in which shift[k] + sum of begin_d can be negative (C's % and the mathematical remainder
+ * differ there, and the reference's loops never go there), nexpr outside 1 .. 3, mod <= 0, rem outside [0, mod), an empty or
+ * out-of-range axis set, and fields under a layout transformation (EXAMG_LAYOUT_SPLIT_X) -- all before anything is launched. */
+typedef struct examg_colouring {
+  int32_t nexpr;
+  int32_t axes[3];  /* bit d: i_d is a summand */
+  int32_t shift[3];
+  int32_t mod[3];
+  int32_t rem[3];
+} examg_colouring_t;
+
+/* examg_stencil_op restricted to the points of one colour of `col`: the three loop kinds, any dimensionality and entry list, constant
+ * stencils and stencil fields in both coefficient layouts, every argument through its own layout, the same arithmetic (entries folded
+ * left to right, no contraction, ww in the form st->wform names).  Only the colour's points of the box are written, in dst alone.
+ * u == dst is an error unless the colouring decouples st.  With nexpr == 1, all axes and mod 2 the result is, bit for bit, that of
+ * examg_stencil_op(..., colour = (rem - shift) mod 2). */
+int examg_stencil_op_coloured(int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs,
+                              const examg_layout_t *ld, double *dst, const examg_stencil_t *st, double w, const examg_colouring_t *col,
+                              const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
+/* One whole multi-colour Gauss-Seidel sweep of a block without neighbours: all mod[0] * mod[1] * .. colour loops of EXAMG_SMOOTH in
+ * place on u, in the reference's order (col->rem is ignored) -- `color with { e_0, .., loop over u { u += ww * (rhs - A * u) } }`.
+ * Bit-identical to that many examg_stencil_op_coloured calls.  Refuses a colouring that does not decouple st.
+ * 27-entry stencil fields in the record layout under the axis-parity colouring `i0 % 2, i1 % 2, i2 % 2` (any shifts) run the colours
+ * (0, c1, c2) and (1, c1, c2) in ONE launch (examg_mcgs_one_pass_eligible): a point of the second has exactly two neighbours in the
+ * first, (x +- 1, y, z) in its own row, and no other point written by either loop is a neighbour of a point written by either; one
+ * wave owns a whole row, updates its first x colour, makes the values visible to itself and updates the second from them.  A sweep is
+ * 4 launches instead of 8, and every 216-byte coefficient record is read once. */
+int examg_mcgs_sweep(const examg_layout_t *lu, double *u, const examg_layout_t *lf, const double *rhs, const examg_stencil_t *st, double w,
+                     const examg_colouring_t *col, const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
+/* 1 if examg_mcgs_sweep runs its row-pair kernel for these arguments, 0 if it issues the colour loops one by one: 3-D, the colouring
+ * `(s0 + i0) % 2, (s1 + i1) % 2, (s2 + i2) % 2`, a 27-entry stencil field of reach 1 under EXAMG_CLAYOUT_ENTRY_FASTEST with the
+ * centre entry first, untransformed layouts. */
+int examg_mcgs_one_pass_eligible(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const examg_colouring_t *col,
+                                 const int32_t *begin, const int32_t *end);
+
 /* One full red-black sweep (colour `first`, then the other) out of place, in ONE pass over HBM: the points of
  * [begin,end) of u_out receive exactly (bit for bit) what the two examg_rbgs_colour calls would leave there;
  * outside the box at most the one-stencil-reach shell is touched, and only by copying u_in's values there; the

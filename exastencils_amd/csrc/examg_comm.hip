@@ -412,7 +412,7 @@ int pass_blocks(const char *who, examg_comm_t *comm, const examg_neighbors_t *nb
     for (int i = 0; i < f.n; ++i) {        // first stage on three planes
       slab(begin, end, f.d[i], f.side[i], 3, sb, se);
       if (COL) {                           // tmp = u_in on the slab with the colour's points updated (reads u_in only): one launch
-        if (stencil_colour_passthrough(lu, u_in, lf, rhs, lu, tmp, st, w, first, sb, se, s)) return 1;
+        if (stencil_loop(EXAMG_SMOOTH, lu, u_in, lf, rhs, lu, tmp, st, w, first, sb, se, true, s)) return 1;
       } else if (examg_stencil_op(EXAMG_SMOOTH, lu, u_in, lf, rhs, lu, tmp, st, w, -1, sb, se, s)) {
         return 1;
       }
@@ -421,7 +421,7 @@ int pass_blocks(const char *who, examg_comm_t *comm, const examg_neighbors_t *nb
     for (int i = 0; i < f.n; ++i) {        // second stage on two planes
       slab(begin, end, f.d[i], f.side[i], 2, sb, se);
       if (COL) {
-        if (stencil_colour_passthrough(lu, tmp, lf, rhs, lu, u_out, st, w, 1 - first, sb, se, s)) return 1;
+        if (stencil_loop(EXAMG_SMOOTH, lu, tmp, lf, rhs, lu, u_out, st, w, 1 - first, sb, se, true, s)) return 1;
       } else if (examg_stencil_op(EXAMG_SMOOTH, lu, tmp, lf, rhs, lu, u_out, st, w, -1, sb, se, s)) {
         return 1;
       }

@@ -1,9 +1,11 @@
-// Shared host/device helpers of libexamg (gfx950).
+// Shared helpers of libexamg (gfx950).  Device and host: layouts, boxes, lane exchanges, 16-byte accesses, conv7, point functions.  Host only:
+// what the stencil launchers share -- with_mode / with_order, the fills of the kernels' stencil arguments, the argument checks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/examg.h"
 
@@ -116,9 +118,9 @@ bool small_residual_restrict_ok(const examg_layout_t *lu, const examg_layout_t *
 int launch_small_residual_restrict(const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs, const examg_layout_t *lc,
                                    double *fc, const examg_stencil_t *st, double scale, const Box &cb, hipStream_t s);
 
-// coloured loop out of place with the other colour carried over (kernels_stencil.hip), for the shell passes of examg_comm.hip
-int stencil_colour_passthrough(const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs, const examg_layout_t *ld,
-                               double *dst, const examg_stencil_t *st, double w, int colour, const int32_t *begin, const int32_t *end, hipStream_t s);
+// examg_stencil_op (kernels_stencil.hip) with one more argument, passthru: a coloured loop out of place carries the other colour over (examg_comm.hip)
+int stencil_loop(int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs, const examg_layout_t *ld, double *dst,
+                 const examg_stencil_t *st, double w, int colour, const int32_t *begin, const int32_t *end, bool passthru, hipStream_t s);
 
 #define EXAMG_CHECK_LAUNCH(name)                                   \
   do {                                                             \
@@ -215,11 +217,11 @@ __device__ __forceinline__ double conv7(const Coef7 &k, double c, double xm, dou
   return acc;
 }
 
-// Which canonical 7-point entry order does a constant stencil use?  -1: none of the two.
-static inline int canonical_order7(const examg_stencil_t *st) {
+// Which canonical 7-point entry order do the entries of a stencil (constant or field) have?  -1: none of the two.
+static inline int star7_order(const examg_stencil_t *st) {
   static const int o0[7][3] = {{0, 0, 0}, {-1, 0, 0}, {1, 0, 0}, {0, -1, 0}, {0, 1, 0}, {0, 0, -1}, {0, 0, 1}};
   static const int o1[7][3] = {{0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
-  if (st->nent != 7 || st->cfield) return -1;
+  if (st->nent != 7) return -1;
   bool m0 = true, m1 = true;
   for (int k = 0; k < 7; ++k)
     for (int d = 0; d < 3; ++d) {
@@ -227,6 +229,12 @@ static inline int canonical_order7(const examg_stencil_t *st) {
       m1 = m1 && st->off[k][d] == o1[k][d];
     }
   return m0 ? 0 : (m1 ? 1 : -1);
+}
+static inline int canonical_order7(const examg_stencil_t *st) { return st->cfield ? -1 : star7_order(st); }   // ... and a constant stencil
+
+// 27-entry stencil field, the centre entry first and the diagonal (the unrolled kernels read both from entry 0); callers add their own conditions
+static inline bool stencil_field27(const examg_stencil_t *st) {
+  return st->cfield && st->nent == 27 && st->diag == 0 && st->off[0][0] == 0 && st->off[0][1] == 0 && st->off[0][2] == 0;
 }
 
 static inline int stencil_reach(const examg_stencil_t *st) {
@@ -237,6 +245,64 @@ static inline int stencil_reach(const examg_stencil_t *st) {
       reach = reach > a ? reach : a;
     }
   return reach;
+}
+
+// ---- host side of the stencil launchers: f(std::integral_constant<int, V>{}), V the loop kind / canonical entry order of a call (kernel template arguments)
+template <class F>
+static inline void with_mode(int mode, F &&f) {
+  if (mode == EXAMG_APPLY) f(std::integral_constant<int, EXAMG_APPLY>{});
+  else if (mode == EXAMG_RESIDUAL) f(std::integral_constant<int, EXAMG_RESIDUAL>{});
+  else f(std::integral_constant<int, EXAMG_SMOOTH>{});
+}
+template <class F>
+static inline void with_order(int ord, F &&f) {
+  if (ord == 0) f(std::integral_constant<int, 0>{});
+  else f(std::integral_constant<int, 1>{});
+}
+static inline Coef7 make_coef7(const examg_stencil_t *st) {
+  return Coef7{{st->coef[0], st->coef[1], st->coef[2], st->coef[3], st->coef[4], st->coef[5], st->coef[6]}};
+}
+// linear offsets of the entries in a plain u layout (0 behind the last entry)
+template <int N>
+static inline void fill_u_offsets(long long (&uo)[N], const examg_stencil_t *st, const LayoutDev &lu) {
+  for (int k = 0; k < N; ++k) uo[k] = k < st->nent ? st->off[k][0] + lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2] : 0;
+}
+
+// What StencilDev (kernels_stencil.hip), MCStencil (kernels_multicolour.hip) and StencilCG (kernels_coarse.hip) share: entries, offsets in u,
+// coefficients, the strides of a coefficient field (cplane between entries, cpt between points; 1 and nent under the entry-fastest
+// transformation).  Returns the coefficient layout (lu for a constant stencil, where no kernel uses it).
+template <class SD>
+static inline LayoutDev fill_stencil_dev(SD &sd, const examg_stencil_t *st, const LayoutDev &lu) {
+  sd.nent = st->nent;
+  sd.diag = st->diag;
+  fill_u_offsets(sd.uo, st, lu);
+  for (int k = 0; k < EXAMG_MAX_ENTRIES; ++k) sd.coef[k] = k < st->nent ? st->coef[k] : 0.0;
+  sd.cfield = st->cfield;
+  const LayoutDev lc = st->cfield ? make_layout(&st->clayout) : lu;
+  const bool records = st->cfield && st->ctransform == EXAMG_CLAYOUT_ENTRY_FASTEST;
+  sd.cplane = !st->cfield ? 0 : (records ? 1 : lc.size);
+  sd.cpt = records ? st->nent : 1;
+  return lc;
+}
+
+// The argument checks of examg_stencil_op, examg_stencil_op_coloured and examg_mcgs_sweep, in two parts: each entry point has checks of
+// its own between them; false: error text set
+static inline bool check_stencil_args(const char *who, int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs,
+                                      const examg_layout_t *ld, const double *dst, const examg_stencil_t *st, const int32_t *begin, const int32_t *end) {
+  if (!lu || !u || !ld || !dst || !st || !begin || !end) { set_error("%s: null argument", who); return false; }
+  if (mode < 0 || mode > 2) { set_error("%s: bad mode %d", who, mode); return false; }
+  if (mode != EXAMG_APPLY && (!rhs || !lf)) { set_error("%s: rhs required for mode %d", who, mode); return false; }
+  if (st->nent < 1 || st->nent > EXAMG_MAX_ENTRIES) { set_error("%s: nent %d out of range", who, st->nent); return false; }
+  return true;
+}
+// ... the box (not empty) against the u, dst, rhs and coefficient allocations
+static inline bool check_stencil_box(const char *who, int mode, const examg_layout_t *lu, const examg_layout_t *lf, const examg_layout_t *ld,
+                                     const examg_stencil_t *st, const Box &box) {
+  if (!box_inside(lu, box, stencil_reach(st))) { set_error("%s: box + stencil reach leaves the u allocation", who); return false; }
+  if (!box_inside(ld, box, 0)) { set_error("%s: box leaves the dst allocation", who); return false; }
+  if (mode != EXAMG_APPLY && !box_inside(lf, box, 0)) { set_error("%s: box leaves the rhs allocation", who); return false; }
+  if (st->cfield && !box_inside(&st->clayout, box, 0)) { set_error("%s: box leaves the coefficient allocation", who); return false; }
+  return true;
 }
 
 struct Params4 {

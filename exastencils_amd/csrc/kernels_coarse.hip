@@ -440,21 +440,7 @@ extern "C" int examg_cg_coarse_variant(const examg_layout_t *lu_, double *sol, c
   const LayoutDev lu = make_layout(lu_), lp = make_layout(lp_);
   if (lu.s1 != lp.s1 || lu.s2 != lp.s2) { set_error("examg_cg_coarse: Solution and cgTmp0 layouts must agree"); return 1; }
   StencilCG sd;
-  sd.nent = st->nent;
-  sd.diag = st->diag;
-  for (int k = 0; k < st->nent; ++k) {
-    sd.uo[k] = st->off[k][0] + lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2];
-    sd.coef[k] = st->coef[k];
-  }
-  sd.cfield = st->cfield;
-  sd.cplane = 0;
-  sd.cpt = 1;
-  LayoutDev lc = lu;
-  if (st->cfield) {
-    lc = make_layout(&st->clayout);
-    sd.cplane = lc.size;
-    if (st->ctransform == EXAMG_CLAYOUT_ENTRY_FASTEST) { sd.cplane = 1; sd.cpt = st->nent; }
-  }
+  const LayoutDev lc = fill_stencil_dev(sd, st, lu);
   const long long ldx = box.n0() + 2, ldxy = ldx * (box.n1() + 2), ldtot = ldxy * (box.n2() + 2);
   // the LDS copy of cgTmp0 has a zero halo: right when the box is the whole interior, so that its neighbours are exactly the
   // boundary planes `apply bc` keeps at zero

@@ -208,10 +208,8 @@ static bool is_parity_of_all(const examg_colouring_t *col, int nd) {
 static int check_coloured(const char *who, int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs,
                           const examg_layout_t *ld, const double *dst, const examg_stencil_t *st, const examg_colouring_t *col, bool with_rem,
                           const int32_t *begin, const int32_t *end) {
-  if (!lu || !u || !ld || !dst || !st || !col || !begin || !end) { set_error("%s: null argument", who); return 1; }
-  if (mode < 0 || mode > 2) { set_error("%s: bad mode %d", who, mode); return 1; }
-  if (mode != EXAMG_APPLY && (!rhs || !lf)) { set_error("%s: rhs required for mode %d", who, mode); return 1; }
-  if (st->nent < 1 || st->nent > EXAMG_MAX_ENTRIES) { set_error("%s: nent %d out of range", who, st->nent); return 1; }
+  if (!col) { set_error("%s: null argument", who); return 1; }
+  if (!check_stencil_args(who, mode, lu, u, lf, rhs, ld, dst, st, begin, end)) return 1;
   if (lu->nd < 1 || lu->nd > 3) { set_error("%s: nd %d out of range", who, lu->nd); return 1; }
   if (const char *msg = check_colouring(col, lu->nd, with_rem)) { set_error("%s: colouring: %s", who, msg); return 1; }
   if (lay_split(lu) || lay_split(ld) || (lf && lay_split(lf)) || (st->cfield && lay_split(&st->clayout))) {
@@ -225,11 +223,7 @@ static int check_coloured(const char *who, int mode, const examg_layout_t *lu, c
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 2;
   if (!starts_nonnegative(col, begin)) { set_error("%s: a colour expression can be negative in this box (shift + begin < 0)", who); return 1; }
-  if (!box_inside(lu, box, stencil_reach(st))) { set_error("%s: box + stencil reach leaves the u allocation", who); return 1; }
-  if (!box_inside(ld, box, 0)) { set_error("%s: box leaves the dst allocation", who); return 1; }
-  if (mode != EXAMG_APPLY && !box_inside(lf, box, 0)) { set_error("%s: box leaves the rhs allocation", who); return 1; }
-  if (st->cfield && !box_inside(&st->clayout, box, 0)) { set_error("%s: box leaves the coefficient allocation", who); return 1; }
-  return 0;
+  return check_stencil_box(who, mode, lu, lf, ld, st, box) ? 0 : 1;
 }
 
 // one colour loop on the generic coloured kernel; the arguments have passed check_coloured
@@ -239,21 +233,7 @@ static int launch_coloured(int mode, const examg_layout_t *lu_, const double *u,
   const LayoutDev lu = make_layout(lu_), ld = make_layout(ld_);
   const LayoutDev lf = lf_ ? make_layout(lf_) : lu;
   MCStencil sd;
-  sd.nent = st->nent;
-  sd.diag = st->diag;
-  for (int k = 0; k < EXAMG_MAX_ENTRIES; ++k) {
-    sd.uo[k] = k < st->nent ? st->off[k][0] + lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2] : 0;
-    sd.coef[k] = k < st->nent ? st->coef[k] : 0.0;
-  }
-  sd.cfield = st->cfield;
-  LayoutDev lc = lu;
-  sd.cplane = 0;
-  sd.cpt = 1;
-  if (st->cfield) {
-    lc = make_layout(&st->clayout);
-    sd.cplane = lc.size;
-    if (st->ctransform == EXAMG_CLAYOUT_ENTRY_FASTEST) { sd.cplane = 1; sd.cpt = st->nent; }
-  }
+  const LayoutDev lc = fill_stencil_dev(sd, st, lu);
   sd.wdiv = st->wform == EXAMG_WEIGHT_DIVIDE ? 1 : 0;
 
   MCColour c;
@@ -290,12 +270,9 @@ static int launch_coloured(int mode, const examg_layout_t *lu_, const double *u,
   long long nb = (total + 255) / 256;
   if (nb > 8192) nb = 8192;
   dim3 grid((unsigned)nb), block(256);
-  if (mode == EXAMG_APPLY)
-    hipLaunchKernelGGL((k_stencil_coloured<EXAMG_APPLY>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, sd, w, c, box);
-  else if (mode == EXAMG_RESIDUAL)
-    hipLaunchKernelGGL((k_stencil_coloured<EXAMG_RESIDUAL>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, sd, w, c, box);
-  else
-    hipLaunchKernelGGL((k_stencil_coloured<EXAMG_SMOOTH>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, sd, w, c, box);
+  with_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL((k_stencil_coloured<decltype(M)::value>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, sd, w, c, box);
+  });
   EXAMG_CHECK_LAUNCH("k_stencil_coloured");
   return 0;
 }
@@ -307,8 +284,7 @@ static bool rowpair_route(const examg_layout_t *lu, const examg_layout_t *lf, co
   if (lu->nd != 3 || col->nexpr != 3) return false;
   for (int k = 0; k < 3; ++k)
     if (col->axes[k] != (1 << k) || col->mod[k] != 2) return false;
-  if (!st->cfield || st->nent != 27 || st->ctransform != EXAMG_CLAYOUT_ENTRY_FASTEST || st->diag != 0) return false;
-  if (st->off[0][0] != 0 || st->off[0][1] != 0 || st->off[0][2] != 0 || stencil_reach(st) != 1) return false;
+  if (!stencil_field27(st) || st->ctransform != EXAMG_CLAYOUT_ENTRY_FASTEST || stencil_reach(st) != 1) return false;
   if (lay_split(lu) || lay_split(lf) || lay_split(&st->clayout)) return false;
   if (box.count() == 0) return false;
   return box_inside(lu, box, 1) && box_inside(lf, box, 0) && box_inside(&st->clayout, box, 0);
@@ -318,7 +294,7 @@ static int launch_rowpair(const examg_layout_t *lu_, double *u, const examg_layo
                           const examg_colouring_t *col, const Box &box, hipStream_t s) {
   const LayoutDev lu = make_layout(lu_), lf = make_layout(lf_), lc = make_layout(&st->clayout);
   MCOffsets uo;
-  for (int k = 0; k < 27; ++k) uo.o[k] = st->off[k][0] + lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2];
+  fill_u_offsets(uo.o, st, lu);
   const int bb[3] = {box.b0, box.b1, box.b2}, ee[3] = {box.e0, box.e1, box.e2};
   // first point >= begin with (shift + i) % 2 == r, per axis and remainder (shift + begin >= 0: checked)
   auto first_of = [&](int d, int r) { return bb[d] + (r - (col->shift[d] + bb[d]) % 2 + 2) % 2; };

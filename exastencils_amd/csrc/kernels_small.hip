@@ -224,9 +224,9 @@ static thread_local int g_small_disable = 0;      // examg_debug_small(1): the p
 static SmallStencil small_stencil(const examg_stencil_t *st, const LayoutDev &lu, int LX, int RY) {
   SmallStencil s;
   s.nent = st->nent;
+  fill_u_offsets(s.uo, st, lu);
   for (int k = 0; k < st->nent; ++k) {
     s.lo[k] = st->off[k][0] + LX * (st->off[k][1] + RY * st->off[k][2]);
-    s.uo[k] = st->off[k][0] + lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2];
     s.coef[k] = st->coef[k];
   }
   return s;

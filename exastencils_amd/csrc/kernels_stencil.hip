@@ -720,7 +720,6 @@ k_rbgs_half_split7(LayoutDev lu, double *__restrict__ u, LayoutDev lf, const dou
 }
 
 static thread_local int g_force_generic = 0;  // test hook (debug build only): examg_debug_force_generic
-static thread_local int g_passthru = 0;       // stencil_colour_passthrough (below): coloured loop out of place, the other colour carried over
 // workgroup cap of the unrolled stencil-field kernel: none.  One short-lived workgroup per 256 points, dispatched in order, keeps
 // the front that sweeps the 30 streams (27 coefficient planes, u, rhs, dst) narrow: 512^3, 27 entries: 7.8 ms with 16384
 // grid-striding workgroups, 6.85 ms uncapped (round-2 sweep through examg_debug_sf27_blocks); a tiled form with XCD-contiguous order: 7.7 ms.
@@ -728,7 +727,7 @@ static thread_local int g_sf27_blocks = 1 << 30;
 static thread_local int g_sf27_unrolled = 1;  // examg_debug_sf27(0): 27-entry stencil fields on the generic kernel
 
 // kernels_stencilfield.hip
-bool stencilfield7_ok(const examg_layout_t *lu, const examg_stencil_t *st, const Box &box, int colour);
+bool stencilfield7_enabled();
 int launch_stencilfield7(int mode, const LayoutDev &lu, const double *u, const LayoutDev &lf, const double *rhs, const LayoutDev &ld,
                          double *dst, const LayoutDev &lc, const double *cf, double w, const Box &box, hipStream_t s);
 
@@ -742,21 +741,17 @@ constexpr int RM_RY = EXAMG_RM_RY, RM_WY = EXAMG_RM_WY;
 
 // the row-marching kernel takes boxes whose rows fit one wave -- 400 .. 512 points (level 9: four segments) or 144 .. 256 points (level 8:
 // two segments) -- and that are long enough in y and z; returns the segments per row, 0: not taken
-template <int MODE>
 static int rowmarch_wanted(const Box &box, int colour) {
-  if (MODE == ZM_RESNORM || colour >= 0) return 0;
-  if (g_rm_on == 0) return 0;
+  if (colour >= 0 || g_rm_on == 0) return 0;
   const int nseg = (box.n0() >= 400 && box.n0() <= 512) ? 4 : ((box.n0() >= 144 && box.n0() <= 256) ? 2 : 0);
   if (g_rm_on == 1) return nseg;
   // rows of 144 .. 256 points (256^3 blocks): measured, no gain -- 0.0715 ms (two rows per wave, 16-plane chunks) / 0.0731 (four rows)
   // against 0.0713 for the window kernel (tools/sweep_rowmarch.py 256, profiles/NOTES.md): the two-segment form stays a debug variant
   return (nseg == 4 && box.n1() >= 64 && box.n2() >= 16) ? nseg : 0;
 }
-// padded layouts (even strides) keep the window kernel: it starts its windows on a 16-byte boundary there and every access is
-// aligned already (512^3, 544-double rows: 0.570 ms against 0.589 for the row-marching kernel)
-static bool rowmarch_layout(const LayoutDev &lu, const LayoutDev &lf, const LayoutDev &ld) {
-  const bool even = !(lu.s1 & 1) && !(lu.s2 & 1) && !(lf.s1 & 1) && !(lf.s2 & 1) && !(ld.s1 & 1) && !(ld.s2 & 1);
-  return g_rm_on == 1 || !even;
+// are the row and plane strides of the three layouts all even?  (padded layouts: `align`, field/ir/IR_AddPaddingToFieldLayouts.scala:36-41)
+static bool even_strides(const LayoutDev &lu, const LayoutDev &lf, const LayoutDev &ld) {
+  return !(lu.s1 & 1) && !(lu.s2 & 1) && !(lf.s1 & 1) && !(lf.s2 & 1) && !(ld.s1 & 1) && !(ld.s2 & 1);
 }
 
 template <int MODE, int ORDER>
@@ -791,15 +786,12 @@ static thread_local int g_zm_blocks = -1, g_zm_minchunk = -1, g_zm_remap = -1, g
 template <int MODE, int ORDER>
 static int launch_zmarch(const LayoutDev &lu, const double *u, const LayoutDev &lf, const double *rhs, const LayoutDev &ld,
                          double *dst, const Coef7 &k, double w, const Box &box, hipStream_t s, int colour = -1, int max_waves = 0) {
-  if (const int nseg = rowmarch_wanted<MODE>(box, colour); nseg && rowmarch_layout(lu, lf, ld)) {
-    if (MODE != ZM_RESNORM) return launch_rowmarch<MODE == ZM_RESNORM ? EXAMG_RESIDUAL : MODE, ORDER>(nseg, lu, u, lf, rhs, ld, dst, k, w, box, s);
-  }
   ZMarchGeom g;
   // Padded layouts (`align`, field/ir/IR_AddPaddingToFieldLayouts.scala:36-41) have even row lengths and put the lower duplicate
   // point on an even index: starting the windows one point to the left of an odd box makes every 16-byte load and store of
   // the sweep 16-byte aligned (the extra point is loaded, never stored).  Not possible in the verbatim layout, whose odd
   // strides flip the parity from row to row.  512^3, rows of 544 doubles: 0.62 -> 0.57 ms (tools/lab/stencil_lab.hip).
-  const bool even = !(lu.s1 & 1) && !(lu.s2 & 1) && !(lf.s1 & 1) && !(lf.s2 & 1) && !(ld.s1 & 1) && !(ld.s2 & 1);
+  const bool even = even_strides(lu, lf, ld);
   const int pu = (int)((lu.origin + box.b0) & 1), pf = (int)((lf.origin + box.b0) & 1), pd = (int)((ld.origin + box.b0) & 1);
   const bool shift = even && pu == 1 && pd == 1 && (MODE == EXAMG_APPLY || pf == 1) && lu.ref0 + box.b0 >= 1 &&
                      ld.ref0 + box.b0 >= 1 && (MODE == EXAMG_APPLY || lf.ref0 + box.b0 >= 1);
@@ -854,6 +846,161 @@ static int launch_zmarch(const LayoutDev &lu, const double *u, const LayoutDev &
 int launch_reduce_sum(const double *part, int n, double *result, hipStream_t s);
 size_t reduce_work_doubles();
 
+// ---- examg_stencil_op: which kernel takes a call (stencil_route), the launchers, the entry point that switches on the route ----
+enum StencilRoute { SR_SPLIT_HALF, SR_ROWMARCH, SR_ZMARCH, SR_FIELD7, SR_FIELD27_REC, SR_FIELD27_PLANES, SR_GENERIC };
+
+// The kernel of one stencil loop whose arguments have passed the checks; aliased: u == dst.  Launches nothing, sets no error text.
+// Every condition, threshold and debug override of the dispatch is here, in the order the kernels are tried; the launchers hold geometry only.
+static StencilRoute stencil_route(int mode, const examg_layout_t *lu_, const examg_layout_t *lf_, const examg_layout_t *ld_, const examg_stencil_t *st,
+                                  int colour, const Box &box, bool aliased, bool passthru) {
+  if (g_force_generic) return SR_GENERIC;
+  const int ord = canonical_order7(st);
+  const bool in_place = aliased && memcmp(lu_, ld_, sizeof(*lu_)) == 0;
+  // a field under a layout transformation (colour split): the generic kernel, which forms every address through the transformed
+  // index; the coefficient field of a stencil field has its own transformation (ctransform) and a plain clayout
+  if (lay_split(lu_) || lay_split(ld_) || (lf_ && lay_split(lf_))) {
+    // ... but for the red-black half sweep on the colour-split layout: 32 B per update (k_rbgs_half_split7); the right-hand side on either layout
+    const bool half = mode == EXAMG_SMOOTH && colour >= 0 && in_place && lay_split(lu_) && lu_->nd == 3 && ord >= 0 && box.n0() >= 32 && box_inside(lu_, box, 1);
+    return half ? SR_SPLIT_HALF : SR_GENERIC;
+  }
+  if (passthru && colour >= 0 && !aliased) return SR_GENERIC;      // the one kernel that carries the other colour over
+  const bool colour_ok = colour < 0 || (mode == EXAMG_SMOOTH && in_place);
+  if (lu_->nd == 3 && ord >= 0 && colour_ok && box.n0() >= 64) {
+    // padded layouts (even strides) keep the window kernel: it starts its windows on a 16-byte boundary there and every access is
+    // aligned already (512^3, 544-double rows: 0.570 ms against 0.589 for the row-marching kernel)
+    const LayoutDev lu = make_layout(lu_);
+    const bool rows = rowmarch_wanted(box, colour) && (g_rm_on == 1 || !even_strides(lu, lf_ ? make_layout(lf_) : lu, make_layout(ld_)));
+    return rows ? SR_ROWMARCH : SR_ZMARCH;
+  }
+  // the 7-entry stencil field in the reference's entry order (kernels_stencilfield.hip); transformed coefficient layouts, `omega / diag(A)`: generic kernel
+  if (stencilfield7_enabled() && lu_->nd == 3 && st->cfield && star7_order(st) == 1 && st->diag == 0 && colour < 0 && box.n0() >= 64 &&
+      st->ctransform == EXAMG_CLAYOUT_PLANES && st->wform == EXAMG_WEIGHT_INV_TIMES)
+    return SR_FIELD7;
+  if (g_sf27_unrolled && stencil_field27(st) && colour < 0 && (mode != EXAMG_SMOOTH || st->wform == EXAMG_WEIGHT_INV_TIMES)) {
+    if (st->ctransform == EXAMG_CLAYOUT_ENTRY_FASTEST && lu_->nd == 3) {
+      // the 16-byte loads of the record stream are clamped to the allocation; a pair that starts on the very last double of the
+      // coefficient array would be shifted -- a box that holds the last allocated point (a coefficient layout without ghost or
+      // pad layers) takes the generic kernel instead
+      const LayoutDev lc = make_layout(&st->clayout);
+      if (lidx(lc, box.e0 - 1, box.e1 - 1, box.e2 - 1) != lc.size - 1) return SR_FIELD27_REC;
+    }
+    if (st->ctransform == EXAMG_CLAYOUT_PLANES) return SR_FIELD27_PLANES;
+  }
+  return SR_GENERIC;
+}
+
+// red-black half sweep on the colour-split layout, in place
+static int launch_split_half(const LayoutDev &lu, double *u, const LayoutDev &lf, const double *rhs, const examg_stencil_t *st, double w, int colour,
+                             const Box &box, hipStream_t s) {
+  const Coef7 k = make_coef7(st);
+  SplitGeom g;
+  g.ax0 = box.b0 + lu.ref0;
+  g.ax1 = box.e0 + lu.ref0;
+  g.hb = g.ax0 >> 1;
+  g.nh = ((g.ax1 - 1) >> 1) - g.hb + 1;
+  g.ntx = (g.nh + 63) / 64;
+  g.nty = (box.n1() + SP_WY - 1) / SP_WY;
+  // planes per chunk: enough workgroups for the chip (>= 2048), chunks of at least 16 planes (two planes of start-up each)
+  int zc = box.n2();
+  while (zc > 16 && (long long)g.ntx * g.nty * ((box.n2() + zc - 1) / zc) < 2048) zc = (zc + 1) / 2;
+  g.zc = zc;
+  const int ntz = (box.n2() + zc - 1) / zc;
+  dim3 block(64, SP_WY, 1), grid((unsigned)(g.ntx * g.nty * ntz), 1, 1);
+  with_order(canonical_order7(st), [&](auto O) {
+    hipLaunchKernelGGL((k_rbgs_half_split7<decltype(O)::value>), grid, block, 0, s, lu, u, lf, rhs, k, w, box, colour, g);
+  });
+  EXAMG_CHECK_LAUNCH("k_rbgs_half_split7");
+  return 0;
+}
+
+// 3-D 7-point constant stencil in a canonical order: the row-marching kernel (rows) or the z-march kernel
+static int launch_star7(bool rows, int mode, const LayoutDev &lu, const double *u, const LayoutDev &lf, const double *rhs, const LayoutDev &ld, double *dst,
+                        const examg_stencil_t *st, double w, int colour, const Box &box, hipStream_t s) {
+  const Coef7 k = make_coef7(st);
+  with_mode(mode, [&](auto M) {
+    with_order(canonical_order7(st), [&](auto O) {
+      if (rows) launch_rowmarch<decltype(M)::value, decltype(O)::value>(rowmarch_wanted(box, colour), lu, u, lf, rhs, ld, dst, k, w, box, s);
+      else launch_zmarch<decltype(M)::value, decltype(O)::value>(lu, u, lf, rhs, ld, dst, k, w, box, s, colour);
+    });
+  });
+  EXAMG_CHECK_LAUNCH("k_stencil7_zmarch");
+  return 0;
+}
+
+// 27-entry stencil field: records -- transformed coefficient layout, ONE coefficient stream, transposed through LDS (k_stencilfield27_rec)
+// -- or coefficients in planes (k_stencilfield_unrolled)
+static int launch_sf27(bool records, int mode, const LayoutDev &lu, const double *u, const LayoutDev &lf, const double *rhs, const LayoutDev &ld,
+                       double *dst, const examg_stencil_t *st, double w, const Box &box, hipStream_t s) {
+  const LayoutDev lc = make_layout(&st->clayout);
+  UOffsets uo;
+  fill_u_offsets(uo.o, st, lu);
+  if (records) {
+    const int tiles_x = (box.n0() + 63) / 64;
+    const long long ntiles = (long long)tiles_x * box.n1() * box.n2();
+    const int run = g_sf27_run > 0 ? g_sf27_run : 2;   // 512^3: 1 tile 6.06 ms, 2 tiles 5.71, 4 tiles 5.93, 8 tiles 5.95 (tools/sf27_layouts.py)
+    const long long nwaves = (ntiles + run - 1) / run;
+    dim3 grid((unsigned)((nwaves + SF27_WAVES - 1) / SF27_WAVES)), block(64, SF27_WAVES);
+    with_mode(mode, [&](auto M) {
+      hipLaunchKernelGGL((k_stencilfield27_rec<decltype(M)::value>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, st->cfield, uo, w, box, tiles_x, ntiles, run);
+    });
+    EXAMG_CHECK_LAUNCH("k_stencilfield27_rec");
+    return 0;
+  }
+  long long nb = (box.count() + 255) / 256;
+  if (nb > g_sf27_blocks) nb = g_sf27_blocks;
+  dim3 grid((unsigned)nb), block(256);
+  with_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL((k_stencilfield_unrolled<decltype(M)::value, 27>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, st->cfield, lc.size, uo, 0, w, box);
+  });
+  EXAMG_CHECK_LAUNCH("k_stencilfield_unrolled");
+  return 0;
+}
+
+static int launch_generic(int mode, const LayoutDev &lu, const double *u, const LayoutDev &lf, const double *rhs, const LayoutDev &ld, double *dst,
+                          const examg_stencil_t *st, double w, int colour, const Box &box, int passthru, hipStream_t s) {
+  StencilDev sd;
+  const LayoutDev lc = fill_stencil_dev(sd, st, lu);
+  for (int k = 0; k < st->nent; ++k) {
+    for (int d = 0; d < 3; ++d) sd.o[k][d] = (signed char)st->off[k][d];
+    sd.ro[k] = lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2];
+  }
+  sd.wdiv = st->wform == EXAMG_WEIGHT_DIVIDE ? 1 : 0;
+  const int row_w = colour >= 0 ? (box.n0() + 1) / 2 : box.n0();
+  const long long total = (long long)row_w * box.n1() * box.n2();
+  long long nb = (total + 255) / 256;
+  if (nb > 8192) nb = 8192;
+  dim3 grid((unsigned)nb), block(256);
+  with_mode(mode, [&](auto M) {
+    hipLaunchKernelGGL((k_stencil_generic<decltype(M)::value>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, sd, w, colour, box, row_w, passthru);
+  });
+  EXAMG_CHECK_LAUNCH("k_stencil_generic");
+  return 0;
+}
+
+// examg_stencil_op, and with passthru the shell passes of examg_rbgs_sweep_blocks (examg_comm.hip): `dst = u` on the box followed by the coloured
+// loop from u into dst, as ONE launch -- the generic kernel writes the colour's points and carries the others over.  Same values as the two launches.
+int stencil_loop(int mode, const examg_layout_t *lu_, const double *u, const examg_layout_t *lf_, const double *rhs, const examg_layout_t *ld_, double *dst,
+                 const examg_stencil_t *st, double w, int colour, const int32_t *begin, const int32_t *end, bool passthru, hipStream_t s) {
+  if (!check_stencil_args("examg_stencil_op", mode, lu_, u, lf_, rhs, ld_, dst, st, begin, end)) return 1;
+  if (colour > 1) { set_error("examg_stencil_op: colour must be -1, 0 or 1"); return 1; }
+  const Box box = make_box(begin, end);
+  if (box.count() == 0) return 0;  // empty iteration space (e.g. coarsest level of one fragment with minLevel 0)
+  if (!check_stencil_box("examg_stencil_op", mode, lu_, lf_, ld_, st, box)) return 1;
+  if (u == dst && colour < 0) { set_error("examg_stencil_op: in-place update needs a colour"); return 1; }
+  if (st->cfield && lay_split(&st->clayout)) { set_error("examg_stencil_op: the coefficient layout of a stencil field cannot be colour-split"); return 1; }
+  const LayoutDev lu = make_layout(lu_), ld = make_layout(ld_), lf = lf_ ? make_layout(lf_) : lu;
+  passthru = passthru && colour >= 0 && u != dst;
+  switch (stencil_route(mode, lu_, lf_, ld_, st, colour, box, u == dst, passthru)) {
+    case SR_SPLIT_HALF: return launch_split_half(lu, dst, lf, rhs, st, w, colour, box, s);
+    case SR_ROWMARCH: return launch_star7(true, mode, lu, u, lf, rhs, ld, dst, st, w, colour, box, s);
+    case SR_ZMARCH: return launch_star7(false, mode, lu, u, lf, rhs, ld, dst, st, w, colour, box, s);
+    case SR_FIELD7: return launch_stencilfield7(mode, lu, u, lf, rhs, ld, dst, make_layout(&st->clayout), st->cfield, w, box, s);
+    case SR_FIELD27_REC: return launch_sf27(true, mode, lu, u, lf, rhs, ld, dst, st, w, box, s);
+    case SR_FIELD27_PLANES: return launch_sf27(false, mode, lu, u, lf, rhs, ld, dst, st, w, box, s);
+    case SR_GENERIC: break;
+  }
+  return launch_generic(mode, lu, u, lf, rhs, ld, dst, st, w, colour, box, passthru ? 1 : 0, s);
+}
 }  // namespace examg
 
 using namespace examg;
@@ -896,170 +1043,18 @@ extern "C" int examg_debug_force_generic(int on) {
   g_force_generic = on;
   return old;
 }
+
+// the route of examg_stencil_op (a StencilRoute) for arguments that would pass its checks, under the hooks set on this thread
+extern "C" int examg_debug_stencil_route(int mode, const examg_layout_t *lu, const examg_layout_t *lf, const examg_layout_t *ld, const examg_stencil_t *st,
+                                         int colour, const int32_t *begin, const int32_t *end, int aliased, int passthru) {
+  return stencil_route(mode, lu, lf, ld, st, colour, make_box(begin, end), aliased != 0, passthru != 0);
+}
 #endif
 
-namespace examg {
-// `dst = u` on the box followed by the coloured loop from u into dst (the shell passes of examg_rbgs_sweep_blocks), as ONE launch: the
-// generic kernel writes the colour's points and carries the others over.  Same values as the two launches.
-int stencil_colour_passthrough(const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs, const examg_layout_t *ld,
-                               double *dst, const examg_stencil_t *st, double w, int colour, const int32_t *begin, const int32_t *end, hipStream_t s) {
-  g_passthru = 1;
-  const int rc = examg_stencil_op(EXAMG_SMOOTH, lu, u, lf, rhs, ld, dst, st, w, colour, begin, end, (examg_stream_t)s);
-  g_passthru = 0;
-  return rc;
-}
-}  // namespace examg
-
-extern "C" int examg_stencil_op(int mode, const examg_layout_t *lu_, const double *u, const examg_layout_t *lf_,
-                                const double *rhs, const examg_layout_t *ld_, double *dst, const examg_stencil_t *st,
-                                double w, int colour, const int32_t *begin, const int32_t *end, examg_stream_t stream) {
-  if (!lu_ || !u || !ld_ || !dst || !st || !begin || !end) { set_error("examg_stencil_op: null argument"); return 1; }
-  if (mode < 0 || mode > 2) { set_error("examg_stencil_op: bad mode %d", mode); return 1; }
-  if (mode != EXAMG_APPLY && (!rhs || !lf_)) { set_error("examg_stencil_op: rhs required for mode %d", mode); return 1; }
-  if (st->nent < 1 || st->nent > EXAMG_MAX_ENTRIES) { set_error("examg_stencil_op: nent %d out of range", st->nent); return 1; }
-  if (colour > 1) { set_error("examg_stencil_op: colour must be -1, 0 or 1"); return 1; }
-  const Box box = make_box(begin, end);
-  if (box.count() == 0) return 0;  // empty iteration space (e.g. coarsest level of one fragment with minLevel 0)
-  const int reach = stencil_reach(st);
-  if (!box_inside(lu_, box, reach)) { set_error("examg_stencil_op: box + stencil reach leaves the u allocation"); return 1; }
-  if (!box_inside(ld_, box, 0)) { set_error("examg_stencil_op: box leaves the dst allocation"); return 1; }
-  if (mode != EXAMG_APPLY && !box_inside(lf_, box, 0)) { set_error("examg_stencil_op: box leaves the rhs allocation"); return 1; }
-  if (st->cfield && !box_inside(&st->clayout, box, 0)) { set_error("examg_stencil_op: box leaves the coefficient allocation"); return 1; }
-  if (u == dst && colour < 0) { set_error("examg_stencil_op: in-place update needs a colour"); return 1; }
-
-  const LayoutDev lu = make_layout(lu_), ld = make_layout(ld_);
-  const LayoutDev lf = lf_ ? make_layout(lf_) : lu;
-  hipStream_t s = (hipStream_t)stream;
-
-  // a field under a layout transformation (colour split): the generic kernel, which forms every address through the transformed
-  // index; the coefficient field of a stencil field has its own transformation (ctransform) and a plain clayout
-  const bool transformed = lay_split(lu_) || lay_split(ld_) || (lf_ && lay_split(lf_));
-  if (st->cfield && lay_split(&st->clayout)) { set_error("examg_stencil_op: the coefficient layout of a stencil field cannot be colour-split"); return 1; }
-  const int passthru = (g_passthru && colour >= 0 && u != dst) ? 1 : 0;
-  const bool force_generic = g_force_generic || transformed || passthru;
-  const int ord = canonical_order7(st);
-  if (transformed && !g_force_generic && mode == EXAMG_SMOOTH && colour >= 0 && u == dst && lay_split(lu_) && memcmp(lu_, ld_, sizeof(*lu_)) == 0 &&
-      lu_->nd == 3 && ord >= 0 && box.n0() >= 32 && box_inside(lu_, box, 1)) {
-    // red-black half sweep on the colour-split layout: 32 B per update (k_rbgs_half_split7); the right-hand side on either layout
-    Coef7 k;
-    for (int i = 0; i < 7; ++i) k.c[i] = st->coef[i];
-    SplitGeom g;
-    g.ax0 = box.b0 + lu.ref0;
-    g.ax1 = box.e0 + lu.ref0;
-    g.hb = g.ax0 >> 1;
-    g.nh = ((g.ax1 - 1) >> 1) - g.hb + 1;
-    g.ntx = (g.nh + 63) / 64;
-    g.nty = (box.n1() + SP_WY - 1) / SP_WY;
-    // planes per chunk: enough workgroups for the chip (>= 2048), chunks of at least 16 planes (two planes of start-up each)
-    int zc = box.n2();
-    while (zc > 16 && (long long)g.ntx * g.nty * ((box.n2() + zc - 1) / zc) < 2048) zc = (zc + 1) / 2;
-    g.zc = zc;
-    const int ntz = (box.n2() + zc - 1) / zc;
-    dim3 block(64, SP_WY, 1), grid((unsigned)(g.ntx * g.nty * ntz), 1, 1);
-    if (ord == 0) hipLaunchKernelGGL((k_rbgs_half_split7<0>), grid, block, 0, s, lu, dst, lf, rhs, k, w, box, colour, g);
-    else hipLaunchKernelGGL((k_rbgs_half_split7<1>), grid, block, 0, s, lu, dst, lf, rhs, k, w, box, colour, g);
-    EXAMG_CHECK_LAUNCH("k_rbgs_half_split7");
-    return 0;
-  }
-  const bool colour_ok = colour < 0 || (mode == EXAMG_SMOOTH && u == dst && memcmp(lu_, ld_, sizeof(*lu_)) == 0);
-  if (!force_generic && lu_->nd == 3 && ord >= 0 && colour_ok && box.n0() >= 64) {
-    Coef7 k;
-    for (int i = 0; i < 7; ++i) k.c[i] = st->coef[i];
-#define EXAMG_ZM(M, O) launch_zmarch<M, O>(lu, u, lf, rhs, ld, dst, k, w, box, s, colour)
-    if (ord == 0) {
-      if (mode == EXAMG_APPLY) EXAMG_ZM(EXAMG_APPLY, 0);
-      else if (mode == EXAMG_RESIDUAL) EXAMG_ZM(EXAMG_RESIDUAL, 0);
-      else EXAMG_ZM(EXAMG_SMOOTH, 0);
-    } else {
-      if (mode == EXAMG_APPLY) EXAMG_ZM(EXAMG_APPLY, 1);
-      else if (mode == EXAMG_RESIDUAL) EXAMG_ZM(EXAMG_RESIDUAL, 1);
-      else EXAMG_ZM(EXAMG_SMOOTH, 1);
-    }
-#undef EXAMG_ZM
-    EXAMG_CHECK_LAUNCH("k_stencil7_zmarch");
-    return 0;
-  }
-
-  if (!force_generic && stencilfield7_ok(lu_, st, box, colour)) {
-    const LayoutDev lcf = make_layout(&st->clayout);
-    return launch_stencilfield7(mode, lu, u, lf, rhs, ld, dst, lcf, st->cfield, w, box, s);
-  }
-
-  if (!force_generic && g_sf27_unrolled && st->cfield && st->nent == 27 && colour < 0 && st->diag == 0 && st->off[0][0] == 0 &&
-      st->off[0][1] == 0 && st->off[0][2] == 0 && st->ctransform == EXAMG_CLAYOUT_ENTRY_FASTEST && lu_->nd == 3 &&
-      (mode != EXAMG_SMOOTH || st->wform == EXAMG_WEIGHT_INV_TIMES) &&
-      // the 16-byte loads of the record stream are clamped to the allocation; a pair that starts on the very last double of the
-      // coefficient array would be shifted -- a box that holds the last allocated point (a coefficient layout without ghost or
-      // pad layers) takes the generic kernel instead
-      lidx(make_layout(&st->clayout), box.e0 - 1, box.e1 - 1, box.e2 - 1) != make_layout(&st->clayout).size - 1) {
-    // transformed coefficient layout: ONE coefficient stream, transposed through LDS (k_stencilfield27_rec)
-    const LayoutDev lc27 = make_layout(&st->clayout);
-    UOffsets uo;
-    for (int k = 0; k < 27; ++k) uo.o[k] = st->off[k][0] + lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2];
-    const int tiles_x = (box.n0() + 63) / 64;
-    const long long ntiles = (long long)tiles_x * box.n1() * box.n2();
-    const int run = g_sf27_run > 0 ? g_sf27_run : 2;   // 512^3: 1 tile 6.06 ms, 2 tiles 5.71, 4 tiles 5.93, 8 tiles 5.95 (tools/sf27_layouts.py)
-    const long long nwaves = (ntiles + run - 1) / run;
-    dim3 gridr((unsigned)((nwaves + SF27_WAVES - 1) / SF27_WAVES)), blockr(64, SF27_WAVES);
-#define EXAMG_SF27R(M) hipLaunchKernelGGL((k_stencilfield27_rec<M>), gridr, blockr, 0, s, lu, u, lf, rhs, ld, dst, lc27, st->cfield, uo, w, box, tiles_x, ntiles, run)
-    if (mode == EXAMG_APPLY) EXAMG_SF27R(EXAMG_APPLY);
-    else if (mode == EXAMG_RESIDUAL) EXAMG_SF27R(EXAMG_RESIDUAL);
-    else EXAMG_SF27R(EXAMG_SMOOTH);
-#undef EXAMG_SF27R
-    EXAMG_CHECK_LAUNCH("k_stencilfield27_rec");
-    return 0;
-  }
-
-  if (!force_generic && g_sf27_unrolled && st->cfield && st->nent == 27 && colour < 0 && st->diag == 0 && st->off[0][0] == 0 &&
-      st->off[0][1] == 0 && st->off[0][2] == 0 && st->ctransform == EXAMG_CLAYOUT_PLANES &&
-      (mode != EXAMG_SMOOTH || st->wform == EXAMG_WEIGHT_INV_TIMES)) {
-    const LayoutDev lc27 = make_layout(&st->clayout);
-    UOffsets uo;
-    for (int k = 0; k < 27; ++k) uo.o[k] = st->off[k][0] + lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2];
-    long long nb27 = (box.count() + 255) / 256;
-    if (nb27 > g_sf27_blocks) nb27 = g_sf27_blocks;
-    dim3 grid27((unsigned)nb27), block27(256);
-#define EXAMG_SF27(M) hipLaunchKernelGGL((k_stencilfield_unrolled<M, 27>), grid27, block27, 0, s, lu, u, lf, rhs, ld, dst, lc27, st->cfield, lc27.size, uo, 0, w, box)
-    if (mode == EXAMG_APPLY) EXAMG_SF27(EXAMG_APPLY);
-    else if (mode == EXAMG_RESIDUAL) EXAMG_SF27(EXAMG_RESIDUAL);
-    else EXAMG_SF27(EXAMG_SMOOTH);
-#undef EXAMG_SF27
-    EXAMG_CHECK_LAUNCH("k_stencilfield_unrolled");
-    return 0;
-  }
-
-  StencilDev sd;
-  sd.nent = st->nent;
-  sd.diag = st->diag;
-  for (int k = 0; k < st->nent; ++k) {
-    sd.uo[k] = st->off[k][0] + lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2];
-    sd.coef[k] = st->coef[k];
-    for (int d = 0; d < 3; ++d) sd.o[k][d] = (signed char)st->off[k][d];
-    sd.ro[k] = lu.s1 * st->off[k][1] + lu.s2 * st->off[k][2];
-  }
-  sd.cfield = st->cfield;
-  LayoutDev lc = lu;
-  sd.cplane = 0;
-  sd.cpt = 1;
-  if (st->cfield) {
-    lc = make_layout(&st->clayout);
-    sd.cplane = lc.size;
-    if (st->ctransform == EXAMG_CLAYOUT_ENTRY_FASTEST) { sd.cplane = 1; sd.cpt = st->nent; }
-  }
-  sd.wdiv = st->wform == EXAMG_WEIGHT_DIVIDE ? 1 : 0;
-  const int row_w = colour >= 0 ? (box.n0() + 1) / 2 : box.n0();
-  const long long total = (long long)row_w * box.n1() * box.n2();
-  long long nb = (total + 255) / 256;
-  if (nb > 8192) nb = 8192;
-  dim3 grid((unsigned)nb), block(256);
-  if (mode == EXAMG_APPLY)
-    hipLaunchKernelGGL((k_stencil_generic<EXAMG_APPLY>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, sd, w, colour, box, row_w, passthru);
-  else if (mode == EXAMG_RESIDUAL)
-    hipLaunchKernelGGL((k_stencil_generic<EXAMG_RESIDUAL>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, sd, w, colour, box, row_w, passthru);
-  else
-    hipLaunchKernelGGL((k_stencil_generic<EXAMG_SMOOTH>), grid, block, 0, s, lu, u, lf, rhs, ld, dst, lc, sd, w, colour, box, row_w, passthru);
-  EXAMG_CHECK_LAUNCH("k_stencil_generic");
-  return 0;
+extern "C" int examg_stencil_op(int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs,
+                                const examg_layout_t *ld, double *dst, const examg_stencil_t *st, double w, int colour, const int32_t *begin,
+                                const int32_t *end, examg_stream_t stream) {
+  return stencil_loop(mode, lu, u, lf, rhs, ld, dst, st, w, colour, begin, end, false, (hipStream_t)stream);
 }
 
 // sum over [begin,end) of (rhs - A u)^2: the residual loop and the reduction loop of the norm as one pass, residual not stored
@@ -1070,15 +1065,14 @@ extern "C" int examg_residual_norm2(const examg_layout_t *lu_, const double *u, 
   const Box box = make_box(begin, end);
   hipStream_t s = (hipStream_t)stream;
   if (box.count() == 0) return check_hip(hipMemsetAsync(result, 0, sizeof(double), s), "examg_residual_norm2 memset");
-  const int ord = canonical_order7(st);
-  if (!g_force_generic && !lay_split(lu_) && !lay_split(lf_) && lu_->nd == 3 && ord >= 0 && box.n0() >= 64 && box_inside(lu_, box, 1) && box_inside(lf_, box, 0)) {
+  // where the residual loop (into an array laid out like u) takes a marching kernel: the z-march kernel with the squares summed
+  const StencilRoute route = stencil_route(EXAMG_RESIDUAL, lu_, lf_, lu_, st, -1, box, false, false);
+  if ((route == SR_ROWMARCH || route == SR_ZMARCH) && box_inside(lu_, box, 1) && box_inside(lf_, box, 0)) {
     const LayoutDev lu = make_layout(lu_), lf = make_layout(lf_);
-    Coef7 k;
-    for (int i = 0; i < 7; ++i) k.c[i] = st->coef[i];
-    int n;      // one partial sum per wave of the grid; a box with more waves than the work buffer holds takes the two-kernel path
+    const Coef7 k = make_coef7(st);
+    int n = 0;  // one partial sum per wave of the grid; a box with more waves than the work buffer holds takes the two-kernel path
     const int cap = (int)reduce_work_doubles();
-    if (ord == 0) n = launch_zmarch<ZM_RESNORM, 0>(lu, u, lf, rhs, lu, (double *)work, k, 0.0, box, s, -1, cap);
-    else n = launch_zmarch<ZM_RESNORM, 1>(lu, u, lf, rhs, lu, (double *)work, k, 0.0, box, s, -1, cap);
+    with_order(canonical_order7(st), [&](auto O) { n = launch_zmarch<ZM_RESNORM, decltype(O)::value>(lu, u, lf, rhs, lu, (double *)work, k, 0.0, box, s, -1, cap); });
     if (n > 0) {
       EXAMG_CHECK_LAUNCH("k_stencil7_zmarch (residual norm)");
       return launch_reduce_sum((const double *)work, n, result, s);

@@ -174,34 +174,20 @@ static void launch_sf(const LayoutDev &lu, const double *u, const LayoutDev &lf,
                      box, g);
 }
 
-template <int MODE>
-static void launch_sf_variant(const LayoutDev &lu, const double *u, const LayoutDev &lf, const double *rhs, const LayoutDev &ld,
-                              double *dst, const LayoutDev &lc, const double *cf, double w, const Box &box, hipStream_t s) {
-  switch (g_sf_variant) {
-    case 1: launch_sf<MODE, 2, 4, 0>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s); break;
-    case 2: launch_sf<MODE, 2, 4, 1>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s); break;
-    case 3: launch_sf<MODE, 1, 4, 2>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s); break;
-    default: launch_sf<MODE, 1, 4, 1>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s); break;
-  }
-}
-
-// Is this the 7-entry stencil field in the reference's entry order, on a box the z-march kernel can take?
-bool stencilfield7_ok(const examg_layout_t *lu, const examg_stencil_t *st, const Box &box, int colour) {
-  static const int o1[7][3] = {{0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
-  if (g_sf_variant < 0 || lu->nd != 3 || st->nent != 7 || !st->cfield || st->diag != 0 || colour >= 0 || box.n0() < 64) return false;
-  if (st->ctransform != EXAMG_CLAYOUT_PLANES) return false;     // transformed coefficient layouts: generic kernel
-  if (st->wform != EXAMG_WEIGHT_INV_TIMES) return false;       // `omega / diag(A)`: generic kernel
-  for (int k = 0; k < 7; ++k)
-    for (int d = 0; d < 3; ++d)
-      if (st->off[k][d] != o1[k][d]) return false;
-  return true;
-}
+// the debug build can switch the kernel off; which stencils and boxes it takes: stencil_route (kernels_stencil.hip)
+bool stencilfield7_enabled() { return g_sf_variant >= 0; }
 
 int launch_stencilfield7(int mode, const LayoutDev &lu, const double *u, const LayoutDev &lf, const double *rhs, const LayoutDev &ld,
                          double *dst, const LayoutDev &lc, const double *cf, double w, const Box &box, hipStream_t s) {
-  if (mode == EXAMG_APPLY) launch_sf_variant<EXAMG_APPLY>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s);
-  else if (mode == EXAMG_RESIDUAL) launch_sf_variant<EXAMG_RESIDUAL>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s);
-  else launch_sf_variant<EXAMG_SMOOTH>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s);
+  with_mode(mode, [&](auto M) {
+    constexpr int MODE = decltype(M)::value;
+    switch (g_sf_variant) {
+      case 1: launch_sf<MODE, 2, 4, 0>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s); break;
+      case 2: launch_sf<MODE, 2, 4, 1>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s); break;
+      case 3: launch_sf<MODE, 1, 4, 2>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s); break;
+      default: launch_sf<MODE, 1, 4, 1>(lu, u, lf, rhs, ld, dst, lc, cf, w, box, s); break;
+    }
+  });
   EXAMG_CHECK_LAUNCH("k_stencilfield7_zmarch");
   return 0;
 }

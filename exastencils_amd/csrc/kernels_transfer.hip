@@ -500,8 +500,7 @@ extern "C" int examg_residual_restrict(const examg_layout_t *lu_, const double *
     return launch_small_residual_restrict(lu_, u, lf_, rhs, lc_, fc, st, scale, cb, (hipStream_t)stream);
   if (residual_restrict_one_pass(lu_, lf_, st, lc_, fbegin, fend, cbegin, cend)) {
     const LayoutDev lu = make_layout(lu_), lf = make_layout(lf_), lc = make_layout(lc_);
-    Coef7 k;
-    for (int i = 0; i < 7; ++i) k.c[i] = st->coef[i];
+    const Coef7 k = make_coef7(st);
     const int ntx = (cb.n0() + 62) / 63;
     // coarse rows per wave: two from 512^3 -> 256^3 (0.520 -> 0.496 ms; 242 VGPRs, two waves per SIMD), one below (256^3 -> 128^3: 0.067 ms
     // against 0.074 with two)
@@ -518,15 +517,11 @@ extern "C" int examg_residual_restrict(const examg_layout_t *lu_, const double *
     const long long nwg = order == 1 ? (long long)ntz * ntx * (((cb.n1() + rw - 1) / rw + 3) / 4) : (nwaves + 3) / 4;
     dim3 grid((unsigned)nwg), block(64, 4, 1);
     hipStream_t s = (hipStream_t)stream;
-#define EXAMG_RR(O, W) hipLaunchKernelGGL((k_residual_restrict3<O, W>), grid, block, 0, s, lu, u, lf, rhs, lc, fc, k, scale, cb, ntx, zc, (int)nwaves, order)
-    if (rw == 2) {
-      if (ord == 0) EXAMG_RR(0, 2);
-      else EXAMG_RR(1, 2);
-    } else {
-      if (ord == 0) EXAMG_RR(0, 1);
-      else EXAMG_RR(1, 1);
-    }
-#undef EXAMG_RR
+    with_order(ord, [&](auto O) {
+      constexpr int ORD = decltype(O)::value;
+      if (rw == 2) hipLaunchKernelGGL((k_residual_restrict3<ORD, 2>), grid, block, 0, s, lu, u, lf, rhs, lc, fc, k, scale, cb, ntx, zc, (int)nwaves, order);
+      else hipLaunchKernelGGL((k_residual_restrict3<ORD, 1>), grid, block, 0, s, lu, u, lf, rhs, lc, fc, k, scale, cb, ntx, zc, (int)nwaves, order);
+    });
     EXAMG_CHECK_LAUNCH("k_residual_restrict3");
     return 0;
   }

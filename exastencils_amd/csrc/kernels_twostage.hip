@@ -606,8 +606,7 @@ static int launch_two_stage_lds(const examg_layout_t *lu_, const double *u, cons
   g.ax0 = -lu.ref0; g.ax1 = lu.tot0 - lu.ref0;
   g.ay0 = -lu.ref1; g.ay1 = lu.tot1 - lu.ref1;
   g.az0 = -lu.ref2; g.az1 = lu.tot2 - lu.ref2;
-  Coef7 k;
-  for (int i = 0; i < 7; ++i) k.c[i] = st->coef[i];
+  const Coef7 k = make_coef7(st);
   const int ord = canonical_order7(st);
   dim3 block(64, NW, 1), grid(g.nblocks, 1, 1);
   TSProl pr;
@@ -1062,20 +1061,15 @@ static int launch_three_stage_shape(const examg_layout_t *lu_, const double *u, 
   g.ax0 = -lu.ref0; g.ax1 = lu.tot0 - lu.ref0;
   g.ay0 = -lu.ref1; g.ay1 = lu.tot1 - lu.ref1;
   g.az0 = -lu.ref2; g.az1 = lu.tot2 - lu.ref2;
-  Coef7 k;
-  for (int i = 0; i < 7; ++i) k.c[i] = st->coef[i];
+  const Coef7 k = make_coef7(st);
   const int ord = canonical_order7(st);
   const bool nt = g_ts_nt >= 0 ? g_ts_nt != 0 : box.count() * 24LL > 200000000LL;    // the store policy of the two-step passes
   dim3 block(64, NW, 1), grid(g.nblocks, 1, 1);
-#define EXAMG_TS3(ORD, NTV) hipLaunchKernelGGL((k_three_stage7_lds<ORD, NW, NTV, RPW, COL>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g)
-  if (ord == 0) {
-    if (nt) EXAMG_TS3(0, true);
-    else EXAMG_TS3(0, false);
-  } else {
-    if (nt) EXAMG_TS3(1, true);
-    else EXAMG_TS3(1, false);
-  }
-#undef EXAMG_TS3
+  with_order(ord, [&](auto O) {
+    constexpr int ORD = decltype(O)::value;
+    if (nt) hipLaunchKernelGGL((k_three_stage7_lds<ORD, NW, true, RPW, COL>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g);
+    else hipLaunchKernelGGL((k_three_stage7_lds<ORD, NW, false, RPW, COL>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g);
+  });
   EXAMG_CHECK_LAUNCH("k_three_stage7_lds");
   return 0;
 }

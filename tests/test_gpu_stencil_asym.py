@@ -24,8 +24,20 @@ from stencil_cases import APPLY, RESIDUAL, SMOOTH, ExactOps
 from test_gpu_kernels import hip, hip3, hipd, two_stage_variant  # noqa: F401  (fixtures)
 
 from exastencils_amd.layout import FieldLayout
+from exastencils_amd.lib import ivec
 
 pytestmark = pytest.mark.gpu
+
+ROUTES = ("split_half", "rowmarch", "zmarch", "field7", "field27_rec", "field27_planes", "generic")      # enum StencilRoute
+
+
+def stencil_route(hipd, mode, lu, lf, ld, st, colour, b, e, in_place, passthru=False):
+    """The kernel examg_stencil_op takes for these arguments (layouts as FieldLayout), asked of the debug build
+    (examg_debug_stencil_route; nothing is launched): the route under the hooks that are set, and with none set the product library's."""
+    sc = st.c_struct(hipd.ptr)
+    r = hipd.L.examg_debug_stencil_route(int(mode), C.byref(lu.c_struct()), C.byref(lf.c_struct()) if lf is not None else None,
+                                         C.byref(ld.c_struct()), C.byref(sc), int(colour), ivec(b), ivec(e), int(in_place), int(passthru))
+    return ROUTES[r]
 
 
 @pytest.fixture(scope="module")
@@ -144,7 +156,8 @@ def _stencil_op_run(ops, data, lu, lf, st, w, mode, colour, b, e, in_place, seed
 @pytest.mark.parametrize("case", STENCIL_CASES, ids=lambda c: "%s-%s-%s-%s" % (c[0], c[3], c[4], c[5]))
 def test_stencil_op_paths(hip, hipd, orc, ex, case, data):
     """examg_stencil_op, APPLY / RESIDUAL / SMOOTH with colours -1, 0, 1 (27 points: colour loops out of place), on every kernel it
-    dispatches to; the whole u, rhs and destination arrays."""
+    dispatches to; the whole u, rhs and destination arrays.  Every call is first asked for its route: the case's label (the
+    row-marching kernel takes no colour loops: those of its cases are the z-march kernel's)."""
     path, nd, shape, lay, which, kind, orders = case
     lu, lf = layouts(nd, shape, lay)
     b, e = box(nd, shape, which)
@@ -159,6 +172,10 @@ def test_stencil_op_paths(hip, hipd, orc, ex, case, data):
             for mode in (APPLY, RESIDUAL, SMOOTH):
                 for colour in ((-1, 0, 1) if mode == SMOOTH else (-1,)):
                     in_place = colour >= 0 and kind != "27"
+                    want = path if path in ("rowmarch", "zmarch") else "generic"
+                    if path == "rowmarch" and colour >= 0:
+                        want = "zmarch"
+                    assert stencil_route(hipd, mode, lu, lf, lu, st, colour, b, e, in_place) == want, (path, order, mode, colour)
                     g = host(gpu, _stencil_op_run(gpu, data, lu, lf, st, w, mode, colour, b, e, in_place, 100))
                     r = host(R, _stencil_op_run(R, data, lu, lf, st, w, mode, colour, b, e, in_place, 100))
                     assert_same(g, r, "%s %s, mode %d colour %d" % (path, order, mode, colour))

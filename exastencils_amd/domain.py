@@ -14,6 +14,27 @@ from typing import Optional, Sequence, Tuple
 from .lib import GeomC
 
 
+def shrink(b, e, faces, k: int):
+    """Box [b, e) with the planes at every face (d, side) of `faces` moved inwards by k points (k = -1: one point outwards)."""
+    bb, ee = list(b), list(e)
+    for d, side in faces:
+        if side < 0:
+            bb[d] = b[d] + k
+        else:
+            ee[d] = e[d] - k
+    return bb, ee
+
+
+def slab(b, e, d: int, side: int, k: int):
+    """The k planes of box [b, e) next to face (d, side) -- all of them where the box has fewer --, tangentially the whole box."""
+    sb, se = list(b), list(e)
+    if side < 0:
+        se[d] = min(b[d] + k, e[d])
+    else:
+        sb[d] = max(e[d] - k, b[d])
+    return sb, se
+
+
 @dataclass
 class RectDomain:
     nd: int
@@ -95,6 +116,16 @@ class RectDomain:
                 return None
             q[d] %= self.num_blocks[d]          # periodic: the block at the other end (this block itself when there is one)
         return self.rank_of(q)
+
+    def interior_faces(self):
+        """The faces [(d, side)] with a neighbour across them, d outer, side in (-1, 1); none on a lone block, unless a dimension
+        is periodic (the block is then its own neighbour there)."""
+        return [(d, side) for d in range(self.nd) for side in (-1, 1) if self.neighbor(d, side) is not None]
+
+    def physical_faces(self):
+        """The faces [(d, side)] on the domain's boundary, in the same order."""
+        interior = self.interior_faces()
+        return [(d, side) for d in range(self.nd) for side in (-1, 1) if (d, side) not in interior]
 
     def ncells(self, level: int) -> Tuple[int, int, int]:
         return tuple(self.frag_len[d] * (1 << level) if d < self.nd else 0 for d in range(3))

@@ -327,7 +327,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
         for n in nodes:
             if cell and n[0] == "sten" and n[1] not in self.transfer:
                 A = self.stencil(n[1], self._level_of(n[2], fr))
-                if any(sum(1 for c in o if c) > 1 for o in A.offsets):
+                if not A.faces_only:
                     raise Exa4Unsupported("stencil %s on a cell field has entries off the axes (edge / corner ghosts are not set)" % n[1])
             if n[0] == "id" and isinstance(n[1], str):
                 if not cell and re.match(r"^vf_cellCent(er|re)_", n[1]):

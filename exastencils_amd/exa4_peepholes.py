@@ -48,7 +48,7 @@ class Peepholes:
 
     @staticmethod
     def _canonical7(A: Stencil, nd: int) -> bool:
-        return nd == 3 and A.cfield is None and len(A.offsets) == 7 and all(sum(1 for c in o if c) <= 1 for o in A.offsets)
+        return nd == 3 and A.cfield is None and len(A.offsets) == 7 and A.faces_only
 
     def _try_fused_sweep(self, body, first: int, fr: _Frame, only_field=None, zero_input: bool = False, correction_from=None) -> bool:
         """`color with { (i0+i1+i2) % 2, [communicate u] loop over u { u += w (f - A u) } [apply bc to u] }` on one block:

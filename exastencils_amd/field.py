@@ -96,6 +96,11 @@ class Stencil:
         return Stencil(self.offsets, self.coefs, out, self.clayout, 1, self.wform)
 
     @property
+    def faces_only(self) -> bool:
+        """No entry off the axes (5/7-point): a loop over this stencil reads face ghosts only, no edge or corner ghost."""
+        return all(sum(1 for c in o if c != 0) <= 1 for o in self.offsets)
+
+    @property
     def diag_index(self) -> int:
         return self.offsets.index((0, 0, 0))
 

@@ -117,6 +117,13 @@ class FieldLayout:
         }
         return table[name]
 
+    def dup_plane(self, d: int, side: int):
+        """Box of the duplicate plane at face (d, side), tangentially DLB..DRE: where a physical face holds its boundary values."""
+        pb = [self.idx("DLB", t) if t < self.nd else 0 for t in range(3)]
+        pe = [self.idx("DRE", t) if t < self.nd else 1 for t in range(3)]
+        pb[d], pe[d] = (self.idx("DLB", d), self.idx("DLE", d)) if side < 0 else (self.idx("DRB", d), self.idx("DRE", d))
+        return pb, pe
+
     def c_struct(self) -> LayoutC:
         s = LayoutC()
         s.nd = self.nd

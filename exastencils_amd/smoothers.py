@@ -21,7 +21,26 @@ experimental_splitLoopsForAsyncComm) applied to a pair of steps.  On a single bl
 """
 from __future__ import annotations
 
+from .domain import shrink, slab
+
 SMOOTH = 2
+
+
+def beside(ops, side_fn, main_fn, overlap: bool = True, sequential: str = "side_first"):
+    """`side_fn()` on the kernel layer's side stream beside `main_fn()` on the current one: the side stream first waits for everything
+    issued so far, the current stream afterwards for the side stream.  Without a side stream (CPU kernel layer) or without `overlap` the
+    two run one after the other, in the order `sequential` names ("side_first" | "main_first")."""
+    if not (overlap and hasattr(ops, "side_stream")):
+        for fn in (side_fn, main_fn) if sequential == "side_first" else (main_fn, side_fn):
+            fn()
+        return
+    torch, side = ops.torch, ops.side_stream()
+    main = torch.cuda.current_stream(ops.device)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        side_fn()
+    main_fn()
+    main.wait_stream(side)
 
 
 def deep_halo_boxes(ops, domain, S, F, A, b, e, faces):
@@ -34,12 +53,7 @@ def deep_halo_boxes(ops, domain, S, F, A, b, e, faces):
     lay, flay = S.layout, F.layout
     if not faces or any(lay.ghost[d] < 2 or flay.ghost[d] < 1 for d, _ in faces) or not (lay.communicates_ghost and flay.communicates_ghost):
         return None
-    b1, e1 = list(b), list(e)
-    for d, side in faces:
-        if side < 0:
-            b1[d] = b[d] - 1
-        else:
-            e1[d] = e[d] + 1
+    b1, e1 = shrink(b, e, faces, -1)
     if hasattr(ops, "two_stage_eligible") and not ops.two_stage_eligible(S.lc, F.lc, A, b1, e1, list(b), list(e)):
         return None
     return b1, e1
@@ -50,23 +64,99 @@ def _edges_matter(faces) -> bool:
     return len({d for d, _ in faces}) > 1
 
 
-
 def jacobi_triple(ops, comm, domain, S, F, A, w: float, tmp_field) -> bool:
     """Three applications of `Smoother@current` on field S (2 slots) in ONE pass (examg_jacobi3: temporal blocking of depth 3), on a block
     without neighbours: reads slot <active>, writes the other slot, one advance -- the slot three advances make active.  Returns False
     (nothing done) on a block with neighbours: three steps without an exchange would need three ghost layers; the caller runs a pair and
     a step there."""
-    nd = domain.nd
-    if any(domain.neighbor(d, side) is not None for d in range(nd) for side in (-1, 1)) or not hasattr(ops, "jacobi3"):
+    if domain.interior_faces():
         return False
     b, e = domain.loop_bounds(S.layout)
     if hasattr(ops, "three_stage_eligible") and not ops.three_stage_eligible(S.lc, F.lc, A, list(b), list(e)):
         return False        # the entry point would run a step through `tmp` (with a copy of the box) and a pair: the caller's pair + step is cheaper
-    axis_only = all(sum(1 for c in o if c != 0) <= 1 for o in A.offsets)
-    comm.exchange(S, S.active, "ghost", axis_only)      # empty on a single block
+    comm.exchange(S, S.active, "ghost", A.faces_only)      # empty on a single block
     ops.jacobi3(S.lc, S.data(S.active), S.data(S.next), tmp_field.data(), F.lc, F.data(), A, w, b, e)
     S.advance()
     return True
+
+
+def _two_stage_pass(kind: str, ops, comm, domain, S, F, A, w: float, tmp_field, *, overlap: bool, u_out, lone, slot=None, first: int = 0,
+                    copy_planes: bool = True):
+    """Two dependent loops over S's box -- two Jacobi steps (kind "jacobi2") or the two colours of a red-black sweep that starts with
+    colour `first` (kind "rbgs") -- from S's slot `slot` (None: the active one) into array u_out as one pass, by the first route that
+    applies:
+
+      1. no neighbours: `lone(b, e)`, the caller's one-pass call on the whole box
+      2. deep halos (deep_halo_boxes): one exchange, one kernel on the grown box
+      3. the communicator's library call (comm.c_pass; csrc/examg_comm.hip: pass_blocks), which is 4. and 5. in C -- the Python form
+         that follows is the same sequence statement by statement; it serves the CPU kernel layer (gloo tests) and is what the library
+         call is tested against (tests/test_gpu_transport.py)
+      4. deep interior (box shrunk by one point at interior faces for the first loop, by two for the second) + two-point shell: exchange S,
+         first loop on three planes per interior face into tmp, exchange tmp, second loop on two planes into u_out
+      5. ... the shell on the side stream beside the interior where the kernel layer runs the interior as one kernel
+         (examg_two_stage_eligible, the route function the entry point itself switches on -- stencil kind AND entry order, row length, box
+         inside the allocation), else interior first: the fallback of the two-box entry points (short rows on coarse levels, other
+         stencils) uses tmp as scratch for its whole first loop and must finish before the shell work writes tmp.
+
+    A red-black slab starts as a copy of its input and has the colour's points updated; a Jacobi slab is launched straight from its
+    input.  The caller makes u_out current."""
+    assert kind in ("jacobi2", "rbgs")
+    jacobi = kind == "jacobi2"
+    colours = (-1, -1) if jacobi else (first, 1 - first)
+    u_in = S.data(slot)
+    b, e = domain.loop_bounds(S.layout)
+    faces = domain.interior_faces()
+    axis_only = A.faces_only                     # 5/7-point: face ghosts suffice
+    tmp = tmp_field.data()
+    probe = hasattr(ops, "two_stage_eligible")
+
+    def boxes(scratch, b1, e1, b2, e2):
+        if jacobi:                                   # always through tmp: the entry point takes no other scratch
+            ops.jacobi2_boxes(S.lc, u_in, u_out, tmp, F.lc, F.data(), A, w, b1, e1, b2, e2)
+        else:
+            ops.rbgs_sweep_fused_boxes(S.lc, u_in, u_out, scratch, F.lc, F.data(), A, w, first, b1, e1, b2, e2)
+
+    if not faces:
+        comm.exchange(S, slot, "ghost", axis_only)      # empty on a single block
+        lone(b, e)
+        return
+    deep = deep_halo_boxes(ops, domain, S, F, A, b, e, faces)
+    if deep is not None:
+        comm.exchange(S, slot, "ghost", axis_only and not _edges_matter(faces))
+        boxes(None if probe else tmp, deep[0], deep[1], list(b), list(e))      # the CPU kernel layer runs the two loops through a copy
+        return
+    if hasattr(comm, "c_pass") and comm.c_pass(kind, S, u_in, u_out, tmp, F, A, w, first, b, e, axis_only, overlap,
+                                               not copy_planes):
+        return
+    b1, e1 = shrink(b, e, faces, 1)
+    b2, e2 = shrink(b, e, faces, 2)
+    has_interior = all(e2[d] > b2[d] for d in range(domain.nd))
+    fused = probe and has_interior and ops.two_stage_eligible(S.lc, F.lc, A, b1, e1, b2, e2)
+    concurrent = overlap and fused and hasattr(ops, "side_stream")
+
+    def interior():
+        if has_interior:
+            boxes(None if concurrent else tmp, b1, e1, b2, e2)
+
+    def slabs(k, u, out, colour):
+        for d, side in faces:
+            sb, se = slab(b, e, d, side, k)
+            if not jacobi:
+                ops.axpby(S.lc, u, S.lc, out, 1.0, 0.0, sb, se)
+            ops.stencil_op(SMOOTH, S.lc, u, F.lc, F.data(), S.lc, out, A, w, colour, sb, se)
+
+    def shell():
+        comm.exchange(S, slot, "ghost", axis_only)
+        # tmp's duplicate planes on PHYSICAL faces are read by the second loop of the slabs (tangential neighbours) and written by
+        # nobody: bring them over from the input, whatever boundary values the program put there (Dirichlet function, or SetFuncDir
+        # values during an FMG start) -- unless the caller wrote them once (position-only values)
+        for d, side in domain.physical_faces() if copy_planes else ():
+            ops.axpby(S.lc, u_in, S.lc, tmp, 1.0, 0.0, *S.layout.dup_plane(d, side))
+        slabs(3, u_in, tmp, colours[0])
+        comm.exchange(tmp_field, None, "ghost", axis_only)
+        slabs(2, tmp, u_out, colours[1])
+
+    beside(ops, shell, interior, concurrent, sequential="main_first")
 
 
 def jacobi_pair(ops, comm, domain, S, F, A, w: float, tmp_field, overlap: bool = True, correction_from=None):
@@ -75,197 +165,29 @@ def jacobi_pair(ops, comm, domain, S, F, A, w: float, tmp_field, overlap: bool =
     reached through one advance of the out-of-place pass.  tmp_field: scratch field of S's layout whose
     Dirichlet shell holds S's boundary values.  correction_from (single block only): the coarser Solution field whose
     prolongation `Correction@current` adds to S just before the pair -- folded into the pass (examg_jacobi2_prolong)."""
-    nd = domain.nd
-    b, e = domain.loop_bounds(S.layout)
-    src, dst = S.active, S.next
-    faces = [(d, side) for d in range(nd) for side in (-1, 1) if domain.neighbor(d, side) is not None]
-    axis_only = all(sum(1 for c in o if c != 0) <= 1 for o in A.offsets)   # 5/7-point: face ghosts suffice
+    u_in, u_out, Sc = S.data(S.active), S.data(S.next), correction_from
+    assert Sc is None or not domain.interior_faces(), "the folded correction needs a block without neighbours"
 
-    def shrunk(k):
-        bb, ee = list(b), list(e)
-        for d, side in faces:
-            if side < 0:
-                bb[d] = b[d] + k
-            else:
-                ee[d] = e[d] - k
-        return bb, ee
-
-    def slab(d, side, k):
-        """The k planes of the loop's box next to face (d, side), tangentially the whole box."""
-        sb, se = list(b), list(e)
-        if side < 0:
-            se[d] = min(b[d] + k, e[d])
+    def lone(b, e):
+        if Sc is not None:
+            ops.jacobi2_prolong(S.lc, u_in, u_out, tmp_field.data(), F.lc, F.data(), A, w, b, e, Sc.lc, Sc.data())
         else:
-            sb[d] = max(e[d] - k, b[d])
-        return sb, se
+            ops.jacobi2_boxes(S.lc, u_in, u_out, tmp_field.data(), F.lc, F.data(), A, w, b, e, b, e)
 
-    def interior():
-        b1, e1 = shrunk(1)
-        b2, e2 = shrunk(2)
-        if all(e2[d] > b2[d] for d in range(nd)):
-            ops.jacobi2_boxes(S.lc, S.data(src), S.data(dst), tmp_field.data(), F.lc, F.data(), A, w, b1, e1, b2, e2)
-
-    def shell():
-        comm.exchange(S, src, "ghost", axis_only)
-        # tmp's duplicate planes on PHYSICAL faces are read by the second step of the slabs (tangential neighbours) and
-        # written by nobody: bring them over from the source slot, whatever boundary values the program put there
-        # (Dirichlet function, or SetFuncDir values during an FMG start)
-        lay = S.layout
-        for d in range(nd):
-            for side in (-1, 1):
-                if domain.neighbor(d, side) is not None:
-                    continue
-                pb = [lay.idx("DLB", t) if t < nd else 0 for t in range(3)]
-                pe = [lay.idx("DRE", t) if t < nd else 1 for t in range(3)]
-                pb[d], pe[d] = (lay.idx("DLB", d), lay.idx("DLE", d)) if side < 0 else (lay.idx("DRB", d), lay.idx("DRE", d))
-                ops.axpby(S.lc, S.data(src), tmp_field.lc, tmp_field.data(), 1.0, 0.0, pb, pe)
-        for d, side in faces:
-            sb, se = slab(d, side, 3)
-            ops.stencil_op(SMOOTH, S.lc, S.data(src), F.lc, F.data(), tmp_field.lc, tmp_field.data(), A, w, -1, sb, se)
-        comm.exchange(tmp_field, None, "ghost", axis_only)
-        for d, side in faces:
-            sb, se = slab(d, side, 2)
-            ops.stencil_op(SMOOTH, tmp_field.lc, tmp_field.data(), F.lc, F.data(), S.lc, S.data(dst), A, w, -1, sb, se)
-
-    if not faces:
-        comm.exchange(S, src, "ghost", axis_only)      # empty on a single block
-        if correction_from is not None:
-            Sc = correction_from
-            ops.jacobi2_prolong(S.lc, S.data(src), S.data(dst), tmp_field.data(), F.lc, F.data(), A, w, b, e, Sc.lc, Sc.data())
-        else:
-            ops.jacobi2_boxes(S.lc, S.data(src), S.data(dst), tmp_field.data(), F.lc, F.data(), A, w, b, e, b, e)
-        S.advance()
-        return
-    assert correction_from is None, "the folded correction needs a block without neighbours"
-    deep = deep_halo_boxes(ops, domain, S, F, A, b, e, faces)
-    if deep is not None:
-        comm.exchange(S, src, "ghost", axis_only and not _edges_matter(faces))
-        ops.jacobi2_boxes(S.lc, S.data(src), S.data(dst), tmp_field.data(), F.lc, F.data(), A, w, deep[0], deep[1], list(b), list(e))
-        S.advance()
-        return
-    # product path on GPUs: the whole choreography below as ONE library call (csrc/examg_comm.hip: pass_blocks) -- the Python
-    # form that follows is the same sequence statement by statement; it serves the CPU kernel layer (gloo tests) and is what
-    # the library call is tested against (tests/test_gpu_transport.py)
-    if hasattr(comm, "c_pass") and comm.c_pass("jacobi2", S, S.data(src), S.data(dst), tmp_field.data(), F, A, w, 0, b, e, axis_only, overlap):
-        S.advance()
-        return
-
-    # The fallback of examg_jacobi2_boxes (short rows on coarse levels, other stencils) uses tmp as scratch for its whole
-    # first step: it must then finish before the shell work writes tmp -- sequential order, no overlap.
-    # The kernel layer decides (examg_two_stage_eligible, the route function the entry point itself switches on -- stencil kind AND
-    # entry order, row length, box inside the allocation): only then may the shell work on tmp run concurrently on the side stream.
-    b1, e1 = shrunk(1)
-    b2, e2 = shrunk(2)
-    fused = hasattr(ops, "two_stage_eligible") and all(e2[d] > b2[d] for d in range(nd)) and \
-        ops.two_stage_eligible(S.lc, F.lc, A, b1, e1, b2, e2)
-    side_stream = ops.side_stream() if (overlap and fused and hasattr(ops, "side_stream")) else None
-    if side_stream is not None:
-        torch = ops.torch
-        main = torch.cuda.current_stream(ops.device)
-        side_stream.wait_stream(main)                # everything issued so far (u, rhs) is visible to the side stream
-        with torch.cuda.stream(side_stream):
-            shell()
-        interior()
-        main.wait_stream(side_stream)
-    else:
-        interior()
-        shell()
+    _two_stage_pass("jacobi2", ops, comm, domain, S, F, A, w, tmp_field, overlap=overlap, slot=S.active, u_out=u_out, lone=lone)
     S.advance()
 
 
 def rbgs_sweep(ops, comm, domain, S, F, A, w: float, alt, tmp_field, first: int = 0, overlap: bool = True, tmp_planes_valid: bool = False):
     """One red-black sweep of `repeat { color with { (i0+i1+i2) % 2, communicate S; loop over S { S += w (F - A S) };
-    apply bc to S } }` (Benchmark/Poisson3D/3D_FD_Poisson_fromL4.exa4:204-213) on a block WITH neighbours, out of place
-    from S's array into `alt`; returns the array that is free afterwards (S's former one) -- the two change roles.
+    apply bc to S } }` (Benchmark/Poisson3D/3D_FD_Poisson_fromL4.exa4:204-213), out of place from S's array into `alt`; returns the
+    array that is free afterwards (S's former one) -- the two change roles.
 
-    Deep interior (loop box shrunk by one point for the first colour, two for the second): one fused pass that needs no
-    ghost value.  Two-point shell along the interior faces: exchange S, first colour on three planes into tmp, exchange
-    tmp, second colour on two planes into alt -- thin launches on a side stream, concurrent with the interior pass.
-    Both arrays and tmp carry S's Dirichlet values on the physical faces (caller: once, `apply bc` values are
-    position-only); results are bit-identical to the two in-place half sweeps."""
-    nd = domain.nd
-    b, e = domain.loop_bounds(S.layout)
+    With neighbours (_two_stage_pass): both arrays and tmp carry S's Dirichlet values on the physical faces (tmp_planes_valid: the
+    caller wrote tmp's once, `apply bc` values are position-only); results are bit-identical to the two in-place half sweeps."""
     src = S.data()
-    faces = [(d, side) for d in range(nd) for side in (-1, 1) if domain.neighbor(d, side) is not None]
-    axis_only = all(sum(1 for c in o if c != 0) <= 1 for o in A.offsets)
-    if not faces:
-        comm.exchange(S, None, "ghost", axis_only)
-        ops.rbgs_sweep_fused(S.lc, src, alt, F.lc, F.data(), A, w, first, b, e)
-        S.slots[S.active] = alt
-        return src
-
-    def shrunk(k):
-        bb, ee = list(b), list(e)
-        for d, side in faces:
-            if side < 0:
-                bb[d] = b[d] + k
-            else:
-                ee[d] = e[d] - k
-        return bb, ee
-
-    def slab(d, side, k):
-        sb, se = list(b), list(e)
-        if side < 0:
-            se[d] = min(b[d] + k, e[d])
-        else:
-            sb[d] = max(e[d] - k, b[d])
-        return sb, se
-
-    deep = deep_halo_boxes(ops, domain, S, F, A, b, e, faces)
-    if deep is not None:
-        comm.exchange(S, None, "ghost", axis_only and not _edges_matter(faces))
-        scratch = None if hasattr(ops, "two_stage_eligible") else tmp_field.data()      # the CPU kernel layer runs the two loops through a copy
-        ops.rbgs_sweep_fused_boxes(S.lc, src, alt, scratch, F.lc, F.data(), A, w, first, deep[0], deep[1], list(b), list(e))
-        S.slots[S.active] = alt
-        return src
-    if hasattr(comm, "c_pass") and comm.c_pass("rbgs", S, src, alt, tmp_field.data(), F, A, w, first, b, e, axis_only, overlap, tmp_planes_valid):
-        S.slots[S.active] = alt        # one library call did interior + shell (see jacobi_pair)
-        return src
-    b1, e1 = shrunk(1)
-    b2, e2 = shrunk(2)
-    # eligibility of the one-pass kernel is the kernel layer's decision (examg_two_stage_eligible); without it the fallback
-    # needs tmp as scratch on the main stream and everything runs in sequence
-    fused = hasattr(ops, "two_stage_eligible") and all(e2[d] > b2[d] for d in range(nd)) and \
-        ops.two_stage_eligible(S.lc, F.lc, A, b1, e1, b2, e2)
-
-    def interior(scratch):
-        if all(e2[d] > b2[d] for d in range(nd)):
-            ops.rbgs_sweep_fused_boxes(S.lc, src, alt, scratch, F.lc, F.data(), A, w, first, b1, e1, b2, e2)
-
-    def shell():
-        lay, tmp = S.layout, tmp_field.data()
-        comm.exchange(S, None, "ghost", axis_only)
-        for d in range(nd if not tmp_planes_valid else 0):     # tmp's physical-face planes: S's (read tangentially by the second colour)
-            for side in (-1, 1):
-                if domain.neighbor(d, side) is not None:
-                    continue
-                pb = [lay.idx("DLB", t) if t < nd else 0 for t in range(3)]
-                pe = [lay.idx("DRE", t) if t < nd else 1 for t in range(3)]
-                pb[d], pe[d] = (lay.idx("DLB", d), lay.idx("DLE", d)) if side < 0 else (lay.idx("DRB", d), lay.idx("DRE", d))
-                ops.axpby(S.lc, src, S.lc, tmp, 1.0, 0.0, pb, pe)
-        for d, side in faces:                    # first colour on three planes: tmp = S, then the colour's points (reads S only)
-            sb, se = slab(d, side, 3)
-            ops.axpby(S.lc, src, S.lc, tmp, 1.0, 0.0, sb, se)
-            ops.stencil_op(SMOOTH, S.lc, src, F.lc, F.data(), S.lc, tmp, A, w, first, sb, se)
-        comm.exchange(tmp_field, None, "ghost", axis_only)
-        for d, side in faces:                    # second colour on two planes: alt = tmp, then the colour's points (reads tmp only)
-            sb, se = slab(d, side, 2)
-            ops.axpby(S.lc, tmp, S.lc, alt, 1.0, 0.0, sb, se)
-            ops.stencil_op(SMOOTH, S.lc, tmp, F.lc, F.data(), S.lc, alt, A, w, 1 - first, sb, se)
-
-    side_stream = ops.side_stream() if (overlap and fused and hasattr(ops, "side_stream")) else None
-    if side_stream is not None:
-        torch = ops.torch
-        main = torch.cuda.current_stream(ops.device)
-        side_stream.wait_stream(main)
-        with torch.cuda.stream(side_stream):
-            shell()
-        interior(None)
-        main.wait_stream(side_stream)
-    else:
-        # the fallback of the fused pass uses tmp as scratch for its first half sweep: it finishes before the shell writes tmp
-        interior(tmp_field.data())
-        shell()
+    _two_stage_pass("rbgs", ops, comm, domain, S, F, A, w, tmp_field, overlap=overlap, u_out=alt, first=first, copy_planes=not tmp_planes_valid,
+                    lone=lambda b, e: ops.rbgs_sweep_fused(S.lc, src, alt, F.lc, F.data(), A, w, first, b, e))
     S.slots[S.active] = alt
     return src
 
@@ -278,43 +200,16 @@ def overlapped_loop(ops, domain, b, e, exchange_ghost, kernel, overlap: bool = T
     shell -- disjoint slabs, so that accumulating loops (`+=`) stay correct -- follows when the halo is in.  Used for
     the residual (reads Solution's ghosts) and for the restriction (its coarse box shrunk by one point reads no fine ghost).
     `kernel(begin, end)` launches the loop on a sub-box; same bits as exchange + one launch over [b, e)."""
-    nd = domain.nd
-    faces = [(d, side) for d in range(nd) for side in (-1, 1) if domain.neighbor(d, side) is not None]
-    if not faces:
+    faces = domain.interior_faces()
+    ib, ie = shrink(b, e, faces, 1)
+    if not faces or any(ie[d] - ib[d] < 1 for d in range(domain.nd)):      # no neighbours, or a block too thin to have an interior: plain order
         exchange_ghost()
         kernel(b, e)
         return
-    ib, ie = list(b), list(e)
-    for d, side in faces:
-        if side < 0:
-            ib[d] = b[d] + 1
-        else:
-            ie[d] = e[d] - 1
-    if any(ie[d] - ib[d] < 1 for d in range(nd)):      # a block this thin has no interior: plain order
-        exchange_ghost()
-        kernel(b, e)
-        return
-    side_stream = ops.side_stream() if (overlap and hasattr(ops, "side_stream")) else None
-    if side_stream is not None:
-        torch = ops.torch
-        main = torch.cuda.current_stream(ops.device)
-        side_stream.wait_stream(main)
-        with torch.cuda.stream(side_stream):
-            exchange_ghost()
-        kernel(ib, ie)
-        main.wait_stream(side_stream)
-    else:
-        exchange_ghost()
-        kernel(ib, ie)
+    beside(ops, exchange_ghost, lambda: kernel(ib, ie), overlap, sequential="side_first")
     lo, hi = list(b), list(e)
-    for d in range(nd):
+    for d in range(domain.nd):
         for side in (-1, 1):
-            if (d, side) not in faces:
-                continue
-            sb, se = list(lo), list(hi)
-            if side < 0:
-                se[d] = b[d] + 1
-            else:
-                sb[d] = e[d] - 1
-            kernel(sb, se)
-        lo[d], hi[d] = ib[d], ie[d]
+            if (d, side) in faces:
+                kernel(*slab(lo, hi, d, side, 1))
+        lo[d], hi[d] = ib[d], ie[d]            # the slabs of the axes that follow leave out what these covered

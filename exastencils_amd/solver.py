@@ -22,9 +22,10 @@ from typing import Dict, List, Optional, Tuple
 import threading as _threading
 
 from .comm import Communicator
-from .domain import RectDomain
+from .domain import RectDomain, shrink
 from .field import (FN_POLY3D, FN_ZERO, Field, Stencil, laplace_fd, laplace_unit, stencil_field_offsets)
 from .layout import FieldLayout
+from .smoothers import beside, jacobi_pair, overlapped_loop, rbgs_sweep
 
 # stream captures of one process run one at a time (a host with several blocks per process -- one thread each -- captures per block;
 # nothing executes during a capture, so no block waits for another inside it)
@@ -67,7 +68,11 @@ class _Program:
         self.err_history: List[float] = []
         self.cg_iters: List[int] = []
         self._graphs: Dict = {}
+        self._graph_generation = 0
         self._one_pass: Dict[int, bool] = {}
+        self._lone = not self.domain.interior_faces()
+        self._cg_info = self.ops.new_array(4)      # one-call coarse solves: iterations, ..., [3] how often the CG loop ran out of them
+        self._cg_limit_seen = 0
 
     # `loop over <field>` bounds
     def bounds(self, f: Field, reduction: bool = False):
@@ -78,10 +83,6 @@ class _Program:
         """axis_only: the loop that follows reads face ghosts only (5/7-point stencil) -- a communicator created with
         concurrent_ghost_axes then sends all axes in one batch (exastencils_amd/comm.py)."""
         self.comm.exchange(f, slot, what, axis_only)
-
-    @staticmethod
-    def _faces_only(A: Stencil) -> bool:
-        return all(sum(1 for c in o if c != 0) <= 1 for o in A.offsets)
 
     # `apply bc to <field>`  ->  applyBCs<Field>_<level>(slot)
     def apply_bc(self, f: Field, slot: Optional[int] = None):
@@ -97,8 +98,9 @@ class _Program:
         return self.comm.reduce_value(t, "sum")
 
     def _single_block(self) -> bool:
-        """No neighbour across any face (a periodic dimension makes a lone block its own neighbour: the paths with exchanges)."""
-        return self.domain.world_size == 1 and not any(self.domain.periodic)
+        """No neighbour across any face: domain.interior_faces() is empty (a periodic dimension makes a lone block its own neighbour:
+        the paths with exchanges)."""
+        return self._lone
 
     def _one_pass_sweep(self, l: int) -> bool:
         """Does the kernel layer run the red-black sweep of level l as one pass (examg_two_stage_eligible)?"""
@@ -109,14 +111,44 @@ class _Program:
                 self.ops.two_stage_eligible(S.lc, self.RHS[l].lc, self.Laplace[l], b, e, b, e)
         return self._one_pass[l]
 
+    def _fold_pays(self, l: int) -> bool:
+        """The size rule of _folds_prolongation: the fold pays where the pass is bandwidth-bound and large (a read-modify-write loop less)
+        and where the level is launch-bound (rows shorter than 64 points: one kernel less, csrc/kernels_small.hip); in between the separate
+        correction is faster."""
+        b, e = self.bounds(self.Solution[l])
+        return (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]) >= self.cfg.fused_prolong_min_points or (e[0] - b[0]) < 64
+
+    def _sweep_out_of_place(self, l: int, w: float, alts: Dict, b, e, correction_from: Optional[Field] = None, zero_input: bool = False):
+        """One red-black sweep of Solution@l over its box [b, e) on a block without neighbours (the exchange is empty) as ONE out-of-place
+        pass into the level's second array alts[l]; the two arrays then change roles.  The correction loop before the sweep, whose box is the sweep's
+        box (examg_rbgs_sweep_fused_prolong), or the zero field the sweep starts from (examg_rbgs_sweep_fused_zero) ride along."""
+        S, F, A, alt, Sc = self.Solution[l], self.RHS[l], self.Laplace[l], alts[l], correction_from
+        src = S.slots[S.current_slot]
+        if Sc is not None:
+            self.ops.rbgs_sweep_fused_prolong(S.lc, src, alt, F.lc, F.data(), A, w, 0, b, e, Sc.lc, Sc.data())
+        elif zero_input:
+            self.ops.rbgs_sweep_fused_zero(S.lc, alt, F.lc, F.data(), A, w, 0, b, e)
+        else:
+            self.ops.rbgs_sweep_fused(S.lc, src, alt, F.lc, F.data(), A, w, 0, b, e)
+        alts[l], S.slots[S.current_slot] = src, alt
+
+    def _residual_norm_one_pass(self, l: int, slot: Optional[int], axis_only: bool) -> float:
+        """`Residual = RHS - A * Solution` of the Solve loop + the residual's norm as one pass: nothing reads Residual@finest before the
+        cycle writes it again (its own residual pass comes first on every path, with or without neighbours), so the squares are summed
+        where the residual would be stored, over the reduction's box (duplicate planes at interior faces count once), then all-reduced."""
+        S, R, F = self.Solution[l], self.Residual[l], self.RHS[l]
+        self.communicate(S, slot, axis_only=axis_only)
+        b, e = self.bounds(R, reduction=True)
+        t = self.ops.residual_norm2(S.lc, S.data(), F.lc, F.data(), self.Laplace[l], b, e, R.lc, R.data())
+        return math.sqrt(self.comm.reduce_value(t, "sum"))
+
     def _report_cg_limit(self):
         """One-call coarse solves count on the device how often the CG loop ran out of iterations (info[3]); the message the generated
         function prints at that point is appended to the log when the host next looks (end of Solve)."""
-        info = getattr(self, "_cg_info", None)
-        if info is None or not getattr(self.cfg, "fused_coarse", False):
+        if not self.cfg.fused_coarse:
             return
-        n = int(self.ops.to_host(info)[3])
-        for _ in range(n - getattr(self, "_cg_limit_seen", 0)):
+        n = int(self.ops.to_host(self._cg_info)[3])
+        for _ in range(n - self._cg_limit_seen):
             self.log.append("Maximum number of cgs iterations (%d) was exceeded" % self.cfg.cg_max)
         self._cg_limit_seen = n
 
@@ -196,7 +228,6 @@ class SolverFromL4(_Program):
         nc = dom.ncells(lo)
         self.cgTmp0 = Field("cgTmp0", lo, FieldLayout.node(nd, nc, 1, True, True, cfg.align), ops, 1, FN_ZERO)   # :32
         self.cgTmp1 = Field("cgTmp1", lo, FieldLayout.node(nd, nc, 0, True, False, cfg.align), ops, 1, None)     # :33
-        self._cg_info = ops.new_array(4)
         self._agg = None
         k = cfg.agglomerate_level
         if k is not None and (dom.world_size > 1 or any(dom.periodic)) and lo <= k < hi:
@@ -272,18 +303,10 @@ class SolverFromL4(_Program):
 
     def _residual_and_norm(self, l: int) -> float:
         """`Residual = RHS - A * Solution` (statement of Solve@finest) followed by ResNorm()."""
-        cfg = self.cfg
-        if not (cfg.fused_residual_norm and hasattr(self.ops, "residual_norm2")):
-            self._update_residual(l)
-            return self.ResNorm(l)
-        # nothing reads Residual@finest before the cycle writes it again (its own residual pass comes first on every path of
-        # mgCycle, with or without neighbours): the squares are summed where the residual would be stored, over the reduction's
-        # box (duplicate planes at interior faces count once), then all-reduced
-        S, R, A = self.Solution[l], self.Residual[l], self.Laplace[l]
-        self.communicate(S, axis_only=self._faces_only(A))
-        b, e = self.bounds(R, reduction=True)
-        t = self.ops.residual_norm2(S.lc, S.data(), self.RHS[l].lc, self.RHS[l].data(), A, b, e, R.lc, R.data())
-        return math.sqrt(self.comm.reduce_value(t, "sum"))
+        if self.cfg.fused_residual_norm:
+            return self._residual_norm_one_pass(l, None, self.Laplace[l].faces_only)
+        self._update_residual(l)
+        return self.ResNorm(l)
 
     def _deep_residual_restrict(self, l: int) -> bool:
         """`communicate Solution; Residual = RHS - A * Solution; communicate Residual; RHS@coarser = Restriction * Residual` on a block with
@@ -291,17 +314,11 @@ class SolverFromL4(_Program):
         `communicate Residual` would bring -- is evaluated here from the same bits, so the one-pass kernel runs on the WHOLE coarse box
         (its fine footprint reaches one point across every interior face) after one exchange; no shell, no residual array."""
         S, F, R, Fc, A = self.Solution[l], self.RHS[l], self.Residual[l], self.RHS[l - 1], self.Laplace[l]
-        dom = self.domain
-        faces = [(d, side) for d in range(dom.nd) for side in (-1, 1) if dom.neighbor(d, side) is not None]
+        faces = self.domain.interior_faces()
         if (not self.cfg.deep_halo or not faces or any(S.layout.ghost[d] < 2 or F.layout.ghost[d] < 1 for d, _ in faces) or
                 not hasattr(self.ops, "residual_restrict_one_pass")):
             return False
-        fb, fe = [list(x) for x in self.bounds(R)]
-        for d, side in faces:
-            if side < 0:
-                fb[d] -= 1
-            else:
-                fe[d] += 1
+        fb, fe = shrink(*self.bounds(R), faces, -1)
         b, e = self.bounds(Fc)
         if not self.ops.residual_restrict_one_pass(S.lc, F.lc, A, Fc.lc, fb, fe, b, e):
             return False
@@ -324,14 +341,12 @@ class SolverFromL4(_Program):
         def loop(bb, ee):
             self.ops.stencil_op(RESIDUAL, S.lc, S.data(), self.RHS[l].lc, self.RHS[l].data(), R.lc, R.data(), A, 0.0, -1, bb, ee)
 
-        if self.cfg.overlap_transfers and not self._single_block() and self._faces_only(A):
+        if self.cfg.overlap_transfers and not self._single_block() and A.faces_only:
             # `communicate Solution` = duplicate layers (in sequence: the loop reads them) + ghost layers (overlapped)
-            from .smoothers import overlapped_loop
-
             self.communicate(S, None, "dup")
             overlapped_loop(self.ops, self.domain, b, e, lambda: self.communicate(S, None, "ghost", axis_only=True), loop)
         else:
-            self.communicate(S, axis_only=self._faces_only(A))
+            self.communicate(S, axis_only=A.faces_only)
             loop(b, e)
         self.apply_bc(R)
 
@@ -413,15 +428,9 @@ class SolverFromL4(_Program):
             # where three sweeps run as two passes of three colour loops, the separate correction loop + those passes beat the folded
             # first sweep + a pass per remaining sweep (tools/ab_post.py, 512^3, one process: cycle 4.875 -> 4.784 ms; same bits)
             return False
-        S = self.Solution[l]
-        b, e = self.bounds(S)
-        # the fold pays where the pass is bandwidth-bound and large (a read-modify-write loop less) and where the level is launch-bound
-        # (rows shorter than 64 points: one kernel less, csrc/kernels_small.hip); in between the separate correction is faster
-        if (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]) < cfg.fused_prolong_min_points and (e[0] - b[0]) >= 64:
-            return False
         # the kernel layer decides whether its one-pass kernel takes these arguments; without it the entry point runs the plain
         # loops on a copy, which costs more than the separate calls
-        return self._one_pass_sweep(l)
+        return self._fold_pays(l) and self._one_pass_sweep(l)
 
     def _three_colour_passes(self, l: int) -> bool:
         """Does the kernel layer run three colour loops of level l in one pass (examg_rbgs_colours3 with its one-pass kernel)?"""
@@ -452,7 +461,6 @@ class SolverFromL4(_Program):
                 return
             it = 0
             while it < self.cfg.n_smooth:
-                alt = self._sol_alt[l]
                 plain = not (it == 0 and (correction_from is not None or zero_input))
                 if plain and self.cfg.n_smooth - it >= 3 and self._three_colour_passes(l):
                     # three sweeps = six colour loops 0 1 0 1 0 1 = two passes of three (the second starts with colour 1): 2 x 24 B per point
@@ -463,23 +471,13 @@ class SolverFromL4(_Program):
                         self._sol_alt[l], S.slots[0] = S.slots[0], alt
                     it += 3
                     continue
-                if it == 0 and correction_from is not None:
-                    # the correction loop, whose box is the sweep's box, rides along (examg_rbgs_sweep_fused_prolong)
-                    Sc = correction_from
-                    self.ops.rbgs_sweep_fused_prolong(S.lc, S.data(), alt, F.lc, F.data(), A, w, 0, b, e, Sc.lc, Sc.data())
-                elif it == 0 and zero_input:
-                    self.ops.rbgs_sweep_fused_zero(S.lc, alt, F.lc, F.data(), A, w, 0, b, e)
-                else:
-                    self.ops.rbgs_sweep_fused(S.lc, S.data(), alt, F.lc, F.data(), A, w, 0, b, e)
-                self._sol_alt[l], S.slots[0] = S.slots[0], alt
+                self._sweep_out_of_place(l, w, self._sol_alt, b, e, None if it else correction_from, zero_input and it == 0)
                 it += 1
             return
         assert correction_from is None and not zero_input
         if self.cfg.fused_rbgs:
             # blocks with neighbours: fused deep interior + two-point shell with its two exchanges on a side stream
             # (exastencils_amd/smoothers.py: rbgs_sweep); the three arrays carry the Dirichlet planes of the physical faces
-            from .smoothers import rbgs_sweep
-
             tmp = self._sweep_tmp.get(l)
             if tmp is None:
                 tmp = self._sweep_tmp[l] = Field("SolutionSweepTmp", l, S.layout, self.ops, 1, S.bc_fn, S.bc_params)
@@ -489,7 +487,7 @@ class SolverFromL4(_Program):
             return
         for _ in range(self.cfg.n_smooth):
             for colour in (0, 1):
-                self.communicate(S, axis_only=self._faces_only(A))
+                self.communicate(S, axis_only=A.faces_only)
                 self.ops.stencil_op(SMOOTH, S.lc, S.data(), F.lc, F.data(), S.lc, S.data(), A, w, colour, b, e)
                 self.apply_bc(S)
 
@@ -513,7 +511,7 @@ class SolverFromL4(_Program):
         elif self.cfg.fused_residual_restrict and self._deep_residual_restrict(l):
             pass      # deep halos: one exchange of Solution (two ghost layers) and the one-pass kernel on the whole coarse box
         elif (self.cfg.fused_residual_restrict and self.cfg.overlap_transfers and not self._single_block() and
-              self._faces_only(self.Laplace[l]) and hasattr(self.comm, "c_residual_restrict") and
+              self.Laplace[l].faces_only and hasattr(self.comm, "c_residual_restrict") and
               self.comm.c_residual_restrict(self.Solution[l], self.RHS[l], R, self.Laplace[l], Fc, 1.0, *self.bounds(R), *self.bounds(Fc),
                                             axis_only=True, overlap=True)):
             # blocks with neighbours, library transport: the four statements as ONE call (examg_residual_restrict_blocks) -- one-pass
@@ -523,8 +521,6 @@ class SolverFromL4(_Program):
             self._update_residual(l)
             b, e = self.bounds(Fc)
             if self.cfg.overlap_transfers and not self._single_block():
-                from .smoothers import overlapped_loop
-
                 self.communicate(R, None, "dup")
                 overlapped_loop(ops, self.domain, b, e, lambda: self.communicate(R, None, "ghost"),
                                 lambda bb, ee: ops.restrict(R.lc, R.data(), Fc.lc, Fc.data(), 1.0, bb, ee))
@@ -551,21 +547,15 @@ class SolverFromL4(_Program):
             self.communicate(Sc)
             self._smooth(l, correction_from=Sc)
             return
-        side = ops.side_stream() if (self.cfg.overlap_transfers and not self._single_block() and hasattr(ops, "side_stream")) else None
-        if side is not None and hasattr(self.comm, "c_prolong_add") and self.comm.c_prolong_add(Sc, S, b, e, overlap=True):
+        overlap = self.cfg.overlap_transfers and not self._single_block() and hasattr(ops, "side_stream")
+        if overlap and hasattr(self.comm, "c_prolong_add") and self.comm.c_prolong_add(Sc, S, b, e, overlap=True):
             pass      # library transport: exchange + kernel as ONE call (examg_prolong_add_blocks), same split as below
-        elif side is not None:
+        elif overlap:
             # `communicate Solution@coarser`: the interpolation of node values reads duplicate and inner points of the coarse
             # block only (fine node i lies between coarse nodes i/2 and (i+1)/2, both inside [0, n]) -- the ghost part of the
             # exchange runs beside the kernel, the duplicate part (which the kernel reads) before it
-            torch = ops.torch
             self.communicate(Sc, None, "dup")
-            main = torch.cuda.current_stream(ops.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                self.communicate(Sc, None, "ghost")
-            ops.prolong_add(Sc.lc, Sc.data(), S.lc, S.data(), b, e)
-            main.wait_stream(side)
+            beside(ops, lambda: self.communicate(Sc, None, "ghost"), lambda: ops.prolong_add(Sc.lc, Sc.data(), S.lc, S.data(), b, e))
         else:
             self.communicate(Sc)
             ops.prolong_add(Sc.lc, Sc.data(), S.lc, S.data(), b, e)
@@ -604,7 +594,7 @@ class SolverFromL4(_Program):
         ops.axpby(Res.lc, Res.data(), p_.lc, p_.data(), 1.0, 0.0, b, e)        # cgTmp0 = Residual
         self.apply_bc(p_)
         for step in range(self.cfg.cg_max):
-            self.communicate(p_, axis_only=self._faces_only(A))
+            self.communicate(p_, axis_only=A.faces_only)
             b, e = self.bounds(Ap)
             ops.stencil_op(APPLY, p_.lc, p_.data(), None, None, Ap.lc, Ap.data(), A, 0.0, -1, b, e)
             alphaNom = rr
@@ -678,7 +668,7 @@ class SolverFromL4(_Program):
                 for l in sorted(self.Solution)]
 
     def replay_cycle(self):
-        if getattr(self.comm, "generation", 0) != getattr(self, "_graph_generation", 0):
+        if getattr(self.comm, "generation", 0) != self._graph_generation:
             raise RuntimeError("the peer-write regions were re-allocated after this cycle was captured (a larger field was exchanged since): capture again")
         graphs = self._graphs["cycle"]
         if len(graphs) == 1:
@@ -797,7 +787,8 @@ class SolverFromL3(_Program):
         nc = dom.ncells(lo)
         self._func_dir: Dict[int, bool] = {}       # level -> its boundary planes hold SetFuncDir's values (FMG start), not the field's bc
         self._rb_alt, self._rb_tmp = {}, {}
-        self._cg_info = ops.new_array(4)
+        self._pair_tmp: Dict[int, Field] = {}      # level -> scratch field of the two-step Jacobi passes
+        self._deferred_correction: Optional[int] = None      # level whose Correction the FMG start left to the next VCycle on it
         self.VecP = Field("VecP", lo, FieldLayout.node(nd, nc, 1, True, True, cfg.align), ops, 1, FN_ZERO)
         self.VecGradP = Field("VecGradP", lo, FieldLayout.node(nd, nc, 0, False, False, cfg.align), ops, 1, None)
 
@@ -820,18 +811,12 @@ class SolverFromL3(_Program):
 
     def _residual_and_norm(self, l: int) -> float:
         """`UpResidual@finest ( )` followed by `NormResidual_0@finest ( )` (Function Solve)."""
-        cfg, A = self.cfg, self.Laplace[l]
-        if not (cfg.fused_residual_norm and cfg.fused_residual_restrict and self._single_block() and A.cfield is None and
-                l != cfg.min_level and hasattr(self.ops, "residual_norm2")):
-            self.UpResidual(l)
-            return self.NormResidual(l)
-        # nothing reads Residual@finest before the cycle's own residual pass writes it again: the squares are summed where the
-        # residual would be stored (SolverFromL4._residual_and_norm)
-        S, R, F = self.Solution[l], self.Residual[l], self.RHS[l]
-        self.communicate(S, S.active)
-        b, e = self.bounds(R, reduction=True)
-        t = self.ops.residual_norm2(S.lc, S.data(), F.lc, F.data(), A, b, e, R.lc, R.data())
-        return math.sqrt(self.comm.reduce_value(t, "sum"))
+        cfg = self.cfg
+        if (cfg.fused_residual_norm and cfg.fused_residual_restrict and self._single_block() and self.Laplace[l].cfield is None and
+                l != cfg.min_level):
+            return self._residual_norm_one_pass(l, self.Solution[l].active, False)
+        self.UpResidual(l)
+        return self.NormResidual(l)
 
     # Function NormError_0@finest : Real
     def NormError(self, l: int) -> float:
@@ -878,20 +863,9 @@ class SolverFromL3(_Program):
             # below, are the same statements with one launch less.)
             alt = self._sweep_arrays(l)
             if self._single_block():
-                # the exchange is empty; the correction loop before the sweep / the zero field the sweep starts from ride along
-                w = self._w(l)
-                if correction_from is not None:
-                    Sc = correction_from
-                    self.ops.rbgs_sweep_fused_prolong(S.lc, S.data(), alt, F.lc, F.data(), A, w, 0, b, e, Sc.lc, Sc.data())
-                elif zero_input:
-                    self.ops.rbgs_sweep_fused_zero(S.lc, alt, F.lc, F.data(), A, w, 0, b, e)
-                else:
-                    self.ops.rbgs_sweep_fused(S.lc, S.data(), alt, F.lc, F.data(), A, w, 0, b, e)
-                self._rb_alt[l], S.slots[S.active] = S.slots[S.active], alt
+                self._sweep_out_of_place(l, self._w(l), self._rb_alt, b, e, correction_from, zero_input)
                 return
             assert correction_from is None and not zero_input
-            from .smoothers import rbgs_sweep
-
             self.communicate(S, S.active, "dup")       # the ghost part of `communicate Solution` is inside rbgs_sweep
             self._rb_alt[l] = rbgs_sweep(self.ops, self.comm, self.domain, S, F, A, self._w(l), alt, self._rb_tmp[l], 0)
         elif self.cfg.smoother == "mcgs":
@@ -922,13 +896,7 @@ class SolverFromL3(_Program):
         if not (cfg.fused_prolong_min_points > 0 and (jac or rb) and self._single_block() and self.nd == 3 and
                 self.Laplace[l].cfield is None):
             return False
-        S = self.Solution[l]
-        b, e = self.bounds(S)
-        # the fold pays where the pass is bandwidth-bound and large (a read-modify-write loop less) and where the level is launch-bound
-        # (rows shorter than 64 points: one kernel less, csrc/kernels_small.hip); in between the separate correction is faster
-        if (e[0] - b[0]) * (e[1] - b[1]) * (e[2] - b[2]) < cfg.fused_prolong_min_points and (e[0] - b[0]) >= 64:
-            return False
-        return self._one_pass_sweep(l)
+        return self._fold_pays(l) and self._one_pass_sweep(l)
 
     def _starts_from_zero(self, l: int) -> bool:
         """Is `SetSolution@l ( 0 )` (in VCycle@(l+1)) left to the first pre-smoothing sweep of level l?  Its boundary planes must be
@@ -938,6 +906,14 @@ class SolverFromL3(_Program):
                     l != cfg.min_level and l < cfg.max_level and cfg.n_smooth >= 1 and self.Solution[l].bc_fn == FN_ZERO and
                     not self._func_dir.get(l) and self.Laplace[l].cfield is None and self._one_pass_sweep(l))
 
+    def _pair_scratch(self, l: int) -> Field:
+        """Scratch field of the two-step Jacobi passes of level l; its Dirichlet shell holds Solution's boundary values."""
+        if l not in self._pair_tmp:
+            S = self.Solution[l]
+            self._pair_tmp[l] = Field("SolutionTmp", l, S.layout, self.ops, 1, S.bc_fn, S.bc_params)
+            self.apply_bc(self._pair_tmp[l])
+        return self._pair_tmp[l]
+
     def Smoothers(self, l: int, n: int, correction_from: Optional[Field] = None, zero_input: bool = False):
         cfg = self.cfg
         if not (cfg.temporal_blocking and cfg.smoother == "jacobi"):
@@ -946,15 +922,7 @@ class SolverFromL3(_Program):
             return
         assert not zero_input
         # pairs of Smoother calls as one pass over HBM (exastencils_amd/smoothers.py), bit-identical
-        from .smoothers import jacobi_pair
-
-        S = self.Solution[l]
-        if not hasattr(self, "_pair_tmp"):
-            self._pair_tmp = {}
-        tmp = self._pair_tmp.get(l)
-        if tmp is None:
-            tmp = self._pair_tmp[l] = Field("SolutionTmp", l, S.layout, self.ops, 1, S.bc_fn, S.bc_params)
-            self.apply_bc(tmp)
+        S, tmp = self.Solution[l], self._pair_scratch(l)
         k = n
         while k >= 2:
             jacobi_pair(self.ops, self.comm, self.domain, S, self.RHS[l], self.Laplace[l], self._w(l), tmp,
@@ -988,7 +956,7 @@ class SolverFromL3(_Program):
             self._flush_deferred_correction()
             return self.VCycle_0(l)
         if (self.cfg.fused_smooth_residual and self.cfg.smoother == "jacobi" and self.cfg.n_smooth >= 1 and self._single_block() and
-                not solution_is_zero and hasattr(self.ops, "jacobi_residual")):
+                not solution_is_zero):
             # `repeat n times { Smoother@current }` + `UpResidual@current`: the last Smoother call and the residual loop in one pass.
             # Both slots of Solution hold the same boundary values (apply_bc writes every slot), which is what the residual reads
             # around the box.
@@ -1006,7 +974,7 @@ class SolverFromL3(_Program):
             self.Correction(l)
             self.Smoothers(l, self.cfg.n_smooth)
             return
-        if getattr(self, "_deferred_correction", None) == l and not solution_is_zero:
+        if self._deferred_correction == l and not solution_is_zero:
             # first cycle on this level after the FMG start came up from below: its Correction in the first sweep, then ResetBC@coarser
             self._deferred_correction = None
             Sc = self.Solution[l - 1]
@@ -1044,7 +1012,7 @@ class SolverFromL3(_Program):
     def VCycle_0(self, l: int):
         ops, A = self.ops, self.Laplace[l]
         S, R, P, GP = self.Solution[l], self.Residual[l], self.VecP, self.VecGradP
-        if self.cfg.fused_coarse and self._single_block() and hasattr(ops, "cg_coarse"):
+        if self.cfg.fused_coarse and self._single_block():
             # the whole function as one persistent workgroup: alpha from the squared norm, no `apply bc` in this solver
             # (include/examg.h: examg_cg_coarse_variant); reductions in the kernel's fixed order, iteration count stays on the device
             from .lib import CG_ALPHA_FROM_NORM, CG_NO_BC
@@ -1128,7 +1096,7 @@ class SolverFromL3(_Program):
             self.FMG(l + 1)
 
     def _flush_deferred_correction(self):
-        l = getattr(self, "_deferred_correction", None)
+        l = self._deferred_correction
         if l is not None:
             self._deferred_correction = None
             self.Correction(l)
@@ -1168,13 +1136,8 @@ class SolverFromL3(_Program):
                         self._sweep_arrays(l)
         if cfg.temporal_blocking and cfg.smoother == "jacobi":
             # the scratch fields of the two-step passes are part of the set-up (a 43 GB allocation inside Solve shows up there)
-            if not hasattr(self, "_pair_tmp"):
-                self._pair_tmp = {}
             for l in self.levels[1:]:
-                if l not in self._pair_tmp:
-                    S = self.Solution[l]
-                    self._pair_tmp[l] = Field("SolutionTmp", l, S.layout, self.ops, 1, S.bc_fn, S.bc_params)
-                    self.apply_bc(self._pair_tmp[l])
+                self._pair_scratch(l)
 
     # -- hipGraph capture (single block, one-call coarse solve: nothing in FMG / VCycle returns to the host) --------------------
     def _pointer_state(self):
@@ -1190,11 +1153,11 @@ class SolverFromL3(_Program):
         arrays = list(self.VecP.slots) + list(self.VecGradP.slots) + list(self._rb_alt.values())
         for l in self.levels:
             arrays += self.Solution[l].slots + self.RHS[l].slots + self.Residual[l].slots
-        for f in list(self._rb_tmp.values()) + list(getattr(self, "_pair_tmp", {}).values()):
+        for f in list(self._rb_tmp.values()) + list(self._pair_tmp.values()):
             arrays += f.slots
         for t in arrays:
             t.zero_()
-        for f in getattr(self, "_pair_tmp", {}).values():
+        for f in self._pair_tmp.values():
             self.apply_bc(f)
         self._func_dir = {}
         self._deferred_correction = None

@@ -76,9 +76,14 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
         """fuse: run red-black sweeps and pairs of slotted Jacobi steps as single passes over HBM where the program's
         statements allow it (bit-identical results; `fuse=False` issues exactly one launch per loop statement).
         auto_graph: a leveled function without parameters whose statements never return to the host (no reductions, prints or
-        builtins anywhere below it: typically the cycle function) is recorded into a hipGraph at its second call and replayed from
-        then on -- the launch sequence of such a call is fixed once the peepholes and fusions have run, so the interpreter's host
-        work is paid once (default: on with `fuse` on the HIP kernel layer, one block)."""
+        builtins anywhere below it, no assignment to a `Globals` variable: typically the cycle function) is recorded into a hipGraph
+        at its second call.  A later call is a replay only while interpreting it would issue the recorded launches with the recorded
+        scalars: the recording keeps a guard (_graph_guard: the array roles, the values of every global the function can read, the
+        boundary / second-array / stencil-field bookkeeping as it stood at entry, the call site) that is compared before every
+        replay, and a replay leaves the bookkeeping as the recorded call left it; a call under another guard is interpreted, and the
+        function recorded anew when two calls in a row meet the same other guard.
+        Default: on with `fuse` on the HIP kernel layer, one block; `auto_graph=True` is honoured on every kernel layer that has the
+        four graph operations (graph_begin / graph_end / graph_replay / graph_capturing)."""
         self.ast = Parser(text).parse()
         self.k = dict(knowledge or {})
         d = _knowledge.derive(self.k)
@@ -128,10 +133,12 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
         self.fuse_min_row = 3
         self.fuse_min_row_blocks = 64
         on_gpu = hasattr(ops, "torch") and getattr(getattr(ops, "device", None), "type", "cpu") != "cpu"
-        self.auto_graph = bool((fuse if auto_graph is None else auto_graph) and on_gpu and domain.world_size == 1 and not any(domain.periodic))
+        self.auto_graph = bool((fuse and on_gpu if auto_graph is None else auto_graph) and hasattr(ops, "graph_begin") and
+                               domain.world_size == 1 and not any(domain.periodic))
         self._auto_graphs: Dict[Tuple[str, int], object] = {}     # (function, level) -> recorded graph | False (not capturable)
         self._auto_calls: Dict[Tuple[str, int], int] = {}
         self._host_free: Dict[Tuple[str, int], bool] = {}
+        self._graph_reads: Dict[Tuple[str, int], Tuple[str, ...]] = {}     # (function, level) -> globals a recording of it depends on
         self._graph_depth = 0
         self.graph_replays = 0
         self._alt: Dict[Tuple[str, int, int], object] = {}
@@ -644,7 +651,44 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
         """Can a call of this leveled function be issued without ever looking at a device value or doing host-visible work?  Decided
         from the program text: loops without reductions, `communicate` / `apply bc` / `advance`, repeats with literal counts, colour
         blocks, conditions and scalar statements without calls or field accesses, calls of functions that qualify themselves -- and
-        the coarsest-level function when it is the generated CG solver (one kernel)."""
+        the coarsest-level function when it is the generated CG solver (one kernel).  No statement below it may assign to a global
+        (a replay would not); the globals it can read are what _graph_deps returns."""
+        return self._graph_deps(name, lvl) is not None
+
+    def _graph_deps(self, name: str, lvl: int) -> Optional[Tuple[str, ...]]:
+        """None if calls of this function are never recorded, else the names of the globals a recording of it depends on (sorted):
+        every global named in the function or in a function reachable from it -- in scalar arguments of loops, conditions, local
+        declarations, point expressions.  Host work on the program text only."""
+        key = (name, lvl)
+        if not self._host_free_text(name, lvl):
+            return None
+        if key not in self._graph_reads:
+            reads, assigned = self._globals_below(("call", name, None, []), set())
+            if assigned:
+                self._host_free[key] = False
+                return None
+            self._graph_reads[key] = tuple(sorted(reads))
+        return self._graph_reads[key]
+
+    def _globals_below(self, node, seen) -> Tuple[set, set]:
+        """(globals read, globals assigned) by the statements / expressions of `node` and by every function they can call, whatever
+        its level (every declaration of a called name counts: more than a call reaches, never less)."""
+        reads, assigned = set(), set()
+        for n in _walk(node):
+            if len(n) >= 2 and n[0] == "id" and n[1] in self.globals:
+                reads.add(n[1])
+            elif len(n) == 4 and n[0] == "assign" and isinstance(n[2], tuple) and n[2][0] == "id" and n[2][1] in self.globals:
+                assigned.add(n[2][1])
+            elif len(n) == 4 and n[0] == "call" and n[1] in self.functions and n[1] not in seen:
+                seen.add(n[1])
+                for fn in self.functions[n[1]]:
+                    r, a = self._globals_below(("block", list(fn.body)), seen)
+                    reads |= r
+                    assigned |= a
+        return reads, assigned
+
+    def _host_free_text(self, name: str, lvl: int) -> bool:
+        """The structural half of _is_host_free: no statement below the function returns to the host."""
         key = (name, lvl)
         if key in self._host_free:
             return self._host_free[key]
@@ -712,40 +756,70 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                 "cg": (getattr(self, "_cg_tail", None), getattr(self, "_cg_info", None))}
 
     def _restore_host_state(self, st):
-        self._bc_valid, self._bc_epoch, self._alt, self._alt_shell = st["bc_valid"], st["bc_epoch"], st["alt"], st["alt_shell"]
-        self._pair_tmp, self._sf_dirty, self._sf_rec = st["pair_tmp"], st["sf_dirty"], st["sf_rec"]
+        """Impose a saved host state (copies: the saved one stays what it was)."""
+        self._bc_valid, self._bc_epoch, self._alt, self._alt_shell = set(st["bc_valid"]), dict(st["bc_epoch"]), dict(st["alt"]), dict(st["alt_shell"])
+        self._pair_tmp, self._sf_dirty, self._sf_rec = dict(st["pair_tmp"]), dict(st["sf_dirty"]), dict(st["sf_rec"])
         for k, (slots, cur) in st["fields"].items():
-            self.fields[k].slots, self.fields[k].current_slot = slots, cur
+            self.fields[k].slots, self.fields[k].current_slot = list(slots), cur
         for attr, v in zip(("_cg_tail", "_cg_info"), st["cg"]):
             if v is None and hasattr(self, attr):
                 delattr(self, attr)
             elif v is not None:
                 setattr(self, attr, v)
 
+    def _graph_guard(self, key: Tuple[str, int]):
+        """What the launches of a call of the recordable function `key`, and their scalar arguments, are decided from, as it stands
+        now: the array roles; type and value of every global the function can read (_graph_deps); the interpreter's bookkeeping --
+        which boundary planes hold their Dirichlet values, the boundary epochs and the shells of the second arrays, the stencil
+        fields whose entry-fastest copy is out of date, which scratch fields and transformed copies exist -- taken whole; the call
+        site (the liveness scan of the cross-statement fusions reads on into the caller); the switches of the one-pass forms.  Two
+        calls with equal guards issue the same launches.  Host work only, no kernel-layer call."""
+        g = self.globals
+        return (self._roles(), tuple((g[n].__class__, g[n]) for n in self._graph_reads[key]), set(self._bc_valid), dict(self._bc_epoch),
+                dict(self._alt_shell), {k for k, v in self._sf_dirty.items() if v}, set(self._pair_tmp), set(self._sf_rec),
+                [(id(body), i) for body, i, _fr, _loop, _fn in self._cont],
+                (self.fuse, self.fuse_coarse_solver, self.fuse_residual_norm, self.fused_prolong_min_points, self.fuse_min_row,
+                 self.fuse_min_row_blocks, id(getattr(self, "_cg_info", None))))
+
     def _call_through_graph(self, name: str, lvl: int) -> bool:
-        """True if the call was issued as a graph replay.  First call: interpreted (lazily created arrays come into being); second
-        call: recorded -- the interpreter runs the function under a stream capture, nothing executes -- and replayed once;
-        afterwards: replayed, as long as every array is in the role it had when the graph was recorded."""
-        torch = self.ops.torch
+        """True if the call was issued as a graph replay -- never while a loop of the caller's is pending, and never for a function that
+        leaves a loop pending: the launches of such a call are not the function's alone.  First call: interpreted (lazily created arrays
+        come into being); second call: recorded -- the interpreter runs the function while the kernel layer records, nothing executes
+        -- and replayed once; afterwards: replayed whenever the guard (_graph_guard) equals the one the recording was made under,
+        interpreted otherwise -- and recorded anew when two calls in a row meet the same other guard.  After a replay the host state is
+        the one the recorded call left."""
+        ops = self.ops
         key = (name, lvl)
         rec = self._auto_graphs.get(key)
-        if rec is False or torch.cuda.is_current_stream_capturing():
-            return False
-        if rec is None:
+        if rec is False or self._pending is not None or ops.graph_capturing():
+            return False                      # (a pending loop of the caller's: interpretation may absorb it into a pass of this function)
+        guard = self._graph_guard(key) if rec is not None or self._auto_calls.get(key, 0) >= 1 else None
+        fresh = rec is None
+        if not fresh and guard != rec["guard"]:
+            # interpreting this call would not issue what was recorded.  A guard seen for the first time: interpret; the guard the
+            # call before was interpreted under: the program has settled in another state, which is recorded in place of the old one
+            fresh, rec["missed"] = rec["missed"] == guard, guard
+            if not fresh:
+                return False
+        if fresh:
             n = self._auto_calls[key] = self._auto_calls.get(key, 0) + 1
             if n < 2:
                 return False
-            self._flush_pending()
-            before, l0, f0 = self._roles(), self.launches, dict(self.fusions)
+            l0, f0 = self.launches, dict(self.fusions)
             saved = self._host_state()
-            g = torch.cuda.CUDAGraph()
             self._graph_depth += 1
             try:
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                g = ops.graph_begin()
+                try:
                     fn = self._resolve(name, lvl)
                     self._exec_block(fn.body, _Frame(lvl, {}), fn=True)
-                    self._flush_pending()     # a loop the function leaves pending for its caller's next statement: issued here
-                ok = self._roles() == before
+                    # a loop the function leaves pending may end in a one-pass form with its caller's next statement (which need not
+                    # store what the loop alone stores): such a function is interpreted, like one that leaves arrays in other roles
+                    left_pending = self._pending is not None
+                    self._flush_pending()     # (recorded all the same: a recording without a launch draws a warning from the runtime)
+                finally:
+                    ops.graph_end(g)
+                ok = not left_pending and self._roles() == guard[0]
             except (RuntimeError, Exa4Unsupported, _Return):
                 ok = False
             finally:
@@ -758,11 +832,13 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                 self._restore_host_state(saved)
                 self._auto_graphs[key] = False
                 return False
-            rec = self._auto_graphs[key] = {"graph": g, "roles": before, "launches": recorded, "fusions": fused}
-        if self._roles() != rec["roles"]:
-            return False                      # arrays swapped roles since (an odd number of out-of-place sweeps elsewhere): interpret
-        self._flush_pending()
-        rec["graph"].replay()
+            rec = self._auto_graphs[key] = {"graph": g, "guard": guard, "exit": self._host_state(), "launches": recorded, "fusions": fused,
+                                            "missed": None, "replays": 0 if rec is None else rec["replays"]}
+        ops.graph_replay(rec["graph"])
+        if not fresh:
+            self._restore_host_state(rec["exit"])
+        rec["missed"] = None
+        rec["replays"] += 1
         self.launches += rec["launches"]
         for k, v in rec["fusions"].items():
             self.fusions[k] = self.fusions.get(k, 0) + v
@@ -778,7 +854,12 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
         """Record one call of a function (typically the cycle function on the finest level) into a hipGraph and return it;
         `graph.replay()` then re-issues all its kernels without host work.  The call must be free of host-visible
         reductions (a generated coarse-grid CG qualifies through examg_cg_coarse) and must leave every array in the role
-        it had before (an even number of out-of-place sweeps / slot advances)."""
+        it had before (an even number of out-of-place sweeps / slot advances).
+
+        Unlike `auto_graph`, the explicit form checks nothing at a replay: the graph holds the launches and the scalar arguments of
+        the recorded call.  The caller must capture again after changing a global the function reads, after rewriting boundary
+        planes (`loop over .. only ..`, readField) or the coefficients of a stencil field, and after anything else that changes the
+        roles of the arrays; while none of these happens a replay is the call, bit for bit."""
         torch = self.ops.torch
         dev = self.ops.device
         cur = torch.cuda.current_stream(dev)

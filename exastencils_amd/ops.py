@@ -56,6 +56,23 @@ class HipOps:
             self._side = self.torch.cuda.Stream(self.device, priority=0 if os.environ.get("EXAMG_SIDE_PRIORITY") == "0" else -1)
         return self._side
 
+    # -- recording launches into a hipGraph (what Exa4Program's auto_graph needs of a kernel layer) ------------------------------
+    def graph_begin(self):
+        """From here on the launches of this thread are recorded, not executed (torch.cuda.graph); returns the recording."""
+        g = self.torch.cuda.CUDAGraph()
+        ctx = self.torch.cuda.graph(g, capture_error_mode="thread_local")
+        ctx.__enter__()
+        return g, ctx
+
+    def graph_end(self, rec):
+        rec[1].__exit__(None, None, None)
+
+    def graph_replay(self, rec):
+        rec[0].replay()
+
+    def graph_capturing(self) -> bool:
+        return self.torch.cuda.is_current_stream_capturing()
+
     def to_host(self, t):
         return t.detach().cpu().numpy()
 

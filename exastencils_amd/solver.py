@@ -1213,7 +1213,9 @@ class SolverFromL3(_Program):
         numIt = 0
         first = cfg.fmg and use_graph and "cycle_first" in self._graphs
         if first and (res < cfg.tol * resStart or cfg.max_it <= 0):
-            raise RuntimeError("Solve(use_graph=True): no cycle follows the FMG start, whose last correction the first cycle's graph carries")
+            # no cycle follows the FMG start, whose last Correction and ResetBC the first cycle's graph carries: they are issued eagerly
+            # below, as in the eager run (a replay does no host work, so the level they are pending on is noted here)
+            self._deferred_correction, first = hi, False
         while not (res < cfg.tol * resStart or numIt >= cfg.max_it):
             numIt += 1
             if use_graph:

@@ -739,3 +739,28 @@ def test_config4_algorithm_fmg_with_red_black_cycles(hip):
     R.setup()
     R.Solve()
     assert Q.res_history == R.res_history
+
+
+def test_fmg_start_without_a_following_cycle_from_graphs(hip):
+    """`Solve(use_graph=True)` with max_it = 0: the recorded FMG start leaves its last Correction and ResetBC to the first cycle's graph,
+    and no cycle follows -- they are issued eagerly, as `Solve()` does through _flush_deferred_correction: equal fields on every level,
+    equal logs."""
+    from exastencils_amd.solver import ConfigL3, SolverFromL3
+
+    kw = dict(nd=3, min_level=2, max_level=5, smoother="rbgs", omega=1.0, stencil="scaled", restrict_scale=1.0, tol=1e-8, bc_fn=1, fmg=True,
+              fused_rbgs=True, fused_residual_restrict=True, fused_prolong_min_points=1, fused_zero_start=True, fused_residual_norm=True,
+              fused_coarse=True, max_it=0)
+    E = SolverFromL3(ConfigL3(**kw), hip)
+    E.setup()
+    assert E._folds_prolongation(5)
+    assert E.Solve() == 0
+    G = SolverFromL3(ConfigL3(**kw), hip)
+    G.setup()
+    G.capture()
+    assert "cycle_first" in G._graphs
+    assert G.Solve(use_graph=True) == 0
+    assert G.log == E.log and G.res_history == E.res_history and E.log[-1] == "0"
+    for l in range(2, 6):
+        for s in range(E.Solution[l].num_slots):
+            assert np.array_equal(hip.to_host(G.Solution[l].data(s)).view(np.uint64), hip.to_host(E.Solution[l].data(s)).view(np.uint64)), (l, s)
+    assert float(np.abs(hip.to_host(E.Solution[5].data())).max()) > 0.0

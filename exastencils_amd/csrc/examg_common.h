@@ -158,6 +158,19 @@ __device__ __forceinline__ double lane_above0(double v) {   // lane l receives l
   return __hiloint2double(hi, lo);
 }
 
+// XCD bands: workgroups are dealt round-robin to the 8 XCDs; within a z layer every XCD takes a band of consecutive workgroups
+// (x tiles fastest, then coarse rows), so the cache lines that x-adjacent tiles share meet in one L2 (kernels_transfer.hip:
+// k_restrict3_wide).  Shared by the cell transfer kernels (kernels_cell.hip) and the system kernels (kernels_system.hip).
+__device__ __forceinline__ long long xcd_band(long long wg, int wpl) {
+  if ((wpl & 7) == 0) {
+    const int per = wpl >> 3;
+    const long long lz = wg / wpl;
+    const int r = (int)(wg - lz * wpl);
+    return lz * wpl + (r & 7) * per + (r >> 3);
+  }
+  return wg;
+}
+
 // ---- shared by the 7-point kernels (kernels_stencil.hip, kernels_twostage.hip, kernels_stencilfield.hip) ----------
 typedef double d2 __attribute__((ext_vector_type(2)));
 struct __attribute__((packed, aligned(8))) d2u { double a, b; };  // 16-byte access at 8-byte alignment

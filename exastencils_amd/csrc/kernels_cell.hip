@@ -57,19 +57,6 @@ __global__ void __launch_bounds__(256) k_apply_bc_cell(LayoutDev l, double *x, G
 }
 
 // ---- restriction ----------------------------------------------------------------------------------------------------------
-// XCD bands: workgroups are dealt round-robin to the 8 XCDs; within a z layer every XCD takes a band of consecutive workgroups
-// (x tiles fastest, then coarse rows), so the cache lines that x-adjacent tiles share meet in one L2 (kernels_transfer.hip:
-// k_restrict3_wide).
-__device__ __forceinline__ long long xcd_band(long long wg, int wpl) {
-  if ((wpl & 7) == 0) {
-    const int per = wpl >> 3;
-    const long long lz = wg / wpl;
-    const int r = (int)(wg - lz * wpl);
-    return lz * wpl + (r & 7) * per + (r >> 3);
-  }
-  return wg;
-}
-
 // fc(I) = sum_{a, b, c in {0,1}} (scale * 0.5^d) * rf(2I + (a, b, c)), terms added in the entry order of the composed stencil
 // kron(kron(Rx, Ry), Rz) (L4_StencilOps.kron: left entries outer, right entries inner): x offset outermost, then y, then z.
 // VEC: the pair (2I, 2I+1) of every fine row with one aligned 16-byte load.

@@ -61,13 +61,14 @@ from .layout import FieldLayout
 from .exa4_parser import (Exa4SyntaxError, Exa4Unsupported, FunctionDecl, Parser, _COORD, _GRIDW, _MATH, _arith,  # noqa: F401
                           _colour_cond, _colour_expr, _conjuncts, _const_value, _contains, _find_calls, _has_coord, _lower_cond, _parity_expr, _walk)
 
+from .exa4_systems import Systems  # noqa: E402
 from .exa4_common import (APPLY, RESIDUAL, SMOOTH, _FN_2D_ONLY, _FN_ANY_DIM, _FN_WITH_PARAM, _N_FN, _Frame, _Return, fn_eval)  # noqa: E402,F401
 from .exa4_builtins import Builtins  # noqa: E402
 from .exa4_fusion import LazyFusions  # noqa: E402
 from .exa4_peepholes import Peepholes  # noqa: E402
 
 
-class Exa4Program(LazyFusions, Peepholes, Builtins):
+class Exa4Program(LazyFusions, Peepholes, Builtins, Systems):
     """One ExaSlang-4 program bound to a kernel layer (`ops`: HipOps on the GPU), a block decomposition and a
     communicator.  `run()` executes `Function Application`; printed lines are collected in `self.out`."""
 
@@ -332,7 +333,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
             raise Exa4Unsupported("cell and node fields mixed in one loop body")
         cell = locs == {"cell"}
         for n in nodes:
-            if cell and n[0] == "sten" and n[1] not in self.transfer:
+            if cell and n[0] == "sten" and n[1] not in self.transfer and not (n[1] in self._stencil_decls and self._coef_field(n[1]) is not None):
                 A = self.stencil(n[1], self._level_of(n[2], fr))
                 if not A.faces_only:
                     raise Exa4Unsupported("stencil %s on a cell field has entries off the axes (edge / corner ghosts are not set)" % n[1])
@@ -456,6 +457,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                 raise Exa4SyntaxError("stencil %s is not declared" % name)
             if lvl not in self.levels_of(sd.levels):
                 raise Exa4SyntaxError("stencil %s is not declared on level %d" % (name, lvl))
+            if self._coef_field(name) is not None:
+                raise Exa4Unsupported("stencil %s is a point-wise coefficient stencil: it stands only in a system row (P * F) + .. + (L * F)" % name)
             fr = _Frame(lvl, {})
             offs = [tuple(o) + (0,) * (3 - len(o)) for o, _ in sd.entries]
             s = self.stencils[(name, lvl)] = Stencil(offs, [float(self._eval(e, fr)) for _, e in sd.entries])
@@ -723,7 +726,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
             elif k == "repeat":
                 if s[1][0] != "num" or s[2] is not None or not self._host_free_body(s[3], lvl):
                     return False
-            elif k == "color":
+            elif k in ("color", "repeatwith"):
                 if not self._host_free_body(s[2], lvl):
                     return False
             elif k == "levelscope":
@@ -901,9 +904,12 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
     # -- statements -----------------------------------------------------------------------------------------------------
     def _exec_block(self, body: list, fr: _Frame, loop: bool = False, fn: bool = False):
         """loop: the list is a loop body that may run again; fn: a function body (a `return` ends here).  The stack of active lists
-        is what the liveness scan of the cross-statement fusions walks (exa4_fusion.py: _dead_after)."""
+        is what the liveness scan of the cross-statement fusions walks (exa4_fusion.py: _dead_after).  A variable declared in the
+        body of a repeat loop lives for one pass, as in the generated block: the CG of Benchmark/OptFlow2D/2D_FD_OptFlow.exa4 declares
+        `Var alpha` at the end of a pass whose first statements mean the global `alpha`."""
         entry = [body, 0, fr, loop, fn]
         self._cont.append(entry)
+        outer = dict(fr.vars) if loop and any(st[0] == "decl" for st in body) else None
         try:
             i = 0
             while i < len(body):
@@ -912,6 +918,13 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                 i += 1
         finally:
             self._cont.pop()
+            if outer is not None:
+                declared = {st[1] for st in body if st[0] == "decl"}
+                for name in declared:
+                    if name in outer:
+                        fr.vars[name] = outer[name]
+                    else:
+                        fr.vars.pop(name, None)
 
     def _field(self, e, fr: _Frame) -> Tuple[Field, int]:
         if e[0] != "fld":
@@ -987,6 +1000,19 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
                 fr.colour = (c - shift) % 2
                 self._exec_block(s[2], fr)
             fr.colour = saved
+        elif k == "repeatwith":
+            # `repeat with { cond, cond, <statements> }`: the statements once per condition; a colour test becomes the colour of the loops inside
+            if fr.colour is not None or fr.mcolour is not None:
+                raise Exa4Unsupported("repeat with inside a coloured block")
+            cols = [_colour_cond(c, self.nd) for c in s[1]]
+            if any(c is None for c in cols):
+                raise Exa4Unsupported("repeat with: a condition other than c == ((i0 + i1 [+ i2]) % 2)")
+            try:
+                for c in cols:
+                    fr.colour = c
+                    self._exec_block(s[2], fr)
+            finally:
+                fr.colour = None
         elif k == "levelscope":
             if fr.level in self.levels_of(s[1], fr.level):
                 self._exec_block(s[2], fr)
@@ -1190,6 +1216,10 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
         if fr.mcolour is not None:
             return self._exec_loop_multicolour(s, fr)
         boxes, colour = self._loop_boxes(f, only, where, reduction, fr)
+        if any(st[0] == "solve" for st in body):
+            if len(body) != 1 or reduction is not None or only is not None:
+                raise Exa4Unsupported("solve locally beside other statements, in a reduction or in an `only` loop")
+            return self._exec_solve_locally(body[0], boxes, colour, fr)
         if reduction is not None:
             return self._exec_reduction(f, boxes, reduction, body, fr)
         if body and all(st[0] == "assign" and st[2][0] == "sentry" for st in body):
@@ -1283,6 +1313,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins):
             if rhs[0] == "fld":
                 X, xs = self._field(rhs, fr)
                 return ops.axpby(X.lc, X.data(xs), D.lc, D.data(ds), 1.0, 0.0, b, e)
+            if self._exec_system_assign(D, ds, rhs, b, e, colour, fr) or (colour is None and self._exec_pointwise(D, ds, rhs, b, e, fr)):
+                return
             r = self._residual_form(rhs, fr)
             if r is not None:
                 F, fs = self._field(r[0], fr)

@@ -113,7 +113,7 @@ class LazyFusions:
     def _gate(self, s, fr) -> bool:
         """True if `s` was absorbed together with the pending loop (nothing left to execute)."""
         k = s[0]
-        if k in ("decl", "assign", "callstmt", "if", "repeat", "until", "levelscope", "return"):
+        if k in ("decl", "assign", "callstmt", "if", "repeat", "repeatwith", "until", "levelscope", "return"):
             # no field access of their own (what they contain is gated when it executes) -- unless one of their expressions names a
             # field: outside a loop that is an argument of a host-side builtin (printField / writeField / readField, norms of a
             # field), which reads or writes the array NOW.  The pending loop runs first.
@@ -357,7 +357,7 @@ class LazyFusions:
             if READ in (a, b):
                 return READ, ra or rb
             return (WRITTEN if a == WRITTEN and b == WRITTEN else NEITHER), ra or rb
-        if k == "color":
+        if k in ("color", "repeatwith"):
             return self._scan(s[2], lvl, key, True)
         if k == "levelscope":
             try:

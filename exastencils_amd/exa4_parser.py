@@ -6,7 +6,7 @@ AST: tuples.  Expressions: ("num", v) ("str", s) ("id", name, level) ("fld", nam
 ("sentry", name, level, offset) ("call", name, level, args) ("bin", op, a, b) ("neg", a) ("not", a).  Statements: ("decl", ..)
 ("assign", op, lhs, rhs) ("loop", target, only, where, reduction, body) ("comm", phase, what, target) ("applybc", target)
 ("advance", target) ("repeat", n, counter, body) ("until", cond, body) ("if", cond, then, else) ("color", exprs, body)
-("levelscope", levels, body) ("return", expr) ("callstmt", call).  Level specifications: ("single", base, delta) ("all",)
+("levelscope", levels, body) ("return", expr) ("callstmt", call) ("repeatwith", conditions, body) ("solve", jacobi, relax, rows of (unknown, lhs, rhs)).  Level specifications: ("single", base, delta) ("all",)
 ("range", a, b) ("list", items) ("but", spec, spec)."""
 from __future__ import annotations
 
@@ -487,6 +487,21 @@ class Parser:
                 return ("advance", self.postfix())
             if w == "repeat":
                 self.next()
+                if self.at("with") and self.at("{", 1):
+                    # `repeat with { cond_0, cond_1, .., <statements> }` (parsers/l4/L4_Parser.scala:337; baseExt/l4/L4_RepeatLoops.scala): the
+                    # statements run once per condition, which becomes the condition of the loops inside
+                    self.next()
+                    self.next()
+                    conds = []
+                    while True:
+                        conds.append(self.expr())
+                        self.expect(",")
+                        if self.peek().text in _STMT_WORDS:
+                            break
+                    body = []
+                    while not self.accept("}"):
+                        body.append(self.stmt())
+                    return ("repeatwith", conds, body)
                 if self.accept("until"):
                     cond = self.expr()
                     return ("until", cond, self.block())
@@ -527,6 +542,26 @@ class Parser:
                 while not self.accept("}"):
                     body.append(self.stmt())
                 return ("color", colours, body)
+            if w == "solve" and self.at("locally", 1):
+                # `solve locally [with jacobi] [relax w] { unknown => lhs == rhs  .. }` (solver/l4/L4_LocalSolve.scala)
+                self.next()
+                self.next()
+                jacobi = False
+                if self.accept("with"):
+                    self.expect("jacobi")
+                    jacobi = True
+                relax = self.expr() if self.accept("relax") else None
+                self.expect("{")
+                rows = []
+                while not self.accept("}"):
+                    unknown = self.postfix()
+                    self.expect("=>")
+                    eq = self.expr()
+                    if eq[0] != "bin" or eq[1] != "==":
+                        raise Exa4SyntaxError("solve locally: `unknown => lhs == rhs` expected")
+                    rows.append((unknown, eq[2], eq[3]))
+                    self.accept(",")
+                return ("solve", jacobi, relax, rows)
             if w == "return":
                 line = self.next().line
                 if self.peek().line == line and not self.at("}"):

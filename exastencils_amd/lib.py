@@ -41,6 +41,16 @@ class ColouringC(C.Structure):
     _fields_ = [("nexpr", C.c_int32)] + [(n, C.c_int32 * 3) for n in ("axes", "shift", "mod", "rem")]
 
 
+SYS_MAX = 3
+SYS_APPLY, SYS_RESIDUAL = 0, 1
+
+
+class SysC(C.Structure):
+    """examg_sys_t: the arrays of a coupled system of n = 2 or 3 cell fields (include/examg.h)."""
+    _fields_ = [("n", C.c_int32), ("lu", LayoutC), ("lf", LayoutC), ("lg", LayoutC), ("ld", LayoutC), ("u", C.c_void_p * SYS_MAX),
+                ("f", C.c_void_p * SYS_MAX), ("g", C.c_void_p * (SYS_MAX * SYS_MAX)), ("dst", C.c_void_p * SYS_MAX)]
+
+
 MAX_EXPR = 256
 OPS = {"const": 0, "x": 1, "y": 2, "z": 3, "+": 4, "-": 5, "*": 6, "/": 7, "neg": 8, "sin": 9, "cos": 10, "exp": 11, "sinh": 12,
        "cosh": 13, "sqrt": 14, "pow": 15, "tan": 16, "log": 17, "fabs": 18, "max": 19, "min": 20, "tanh": 21}
@@ -88,6 +98,7 @@ SYMBOLS = [
     "examg_sum", "examg_add_scalar", "examg_fill_expr_cell", "examg_max_err_expr_cell", "examg_apply_bc_cell", "examg_restrict_cell",
     "examg_prolong_add_cell",
     "examg_stencil_op_coloured", "examg_mcgs_sweep", "examg_mcgs_one_pass_eligible",
+    "examg_sys_op", "examg_sys_relax", "examg_pointwise_mul",
 ]
 
 COMM_ID_BYTES = 128
@@ -210,6 +221,10 @@ def load(path=None):
     L.examg_stencil_op_coloured.argtypes = [C.c_int, lp, vp, lp, vp, lp, vp, sp, C.c_double, cp, ip, ip, vp]
     L.examg_mcgs_sweep.argtypes = [lp, vp, lp, vp, sp, C.c_double, cp, ip, ip, vp]
     L.examg_mcgs_one_pass_eligible.argtypes = [lp, lp, sp, cp, ip, ip]
+    yp = C.POINTER(SysC)
+    L.examg_sys_op.argtypes = [C.c_int, yp, sp, C.c_uint32, ip, ip, vp]
+    L.examg_sys_relax.argtypes = [yp, sp, C.c_double, C.c_int, ip, ip, vp]
+    L.examg_pointwise_mul.argtypes = [lp, vp, lp, vp, lp, vp, C.c_double, ip, ip, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("examg_version", "examg_last_error", "examg_device_count", "examg_reduce_work_bytes", "examg_exchange_workspace_bytes",
@@ -224,6 +239,9 @@ def load(path=None):
     if hasattr(L, "examg_debug_mcgs_per_colour"):    # debug build only: examg_mcgs_sweep as its colour loops
         L.examg_debug_mcgs_per_colour.argtypes = [C.c_int]
         L.examg_debug_mcgs_per_colour.restype = C.c_int
+    if hasattr(L, "examg_debug_sys_narrow"):         # debug build only: the 8-byte form of the system kernels
+        L.examg_debug_sys_narrow.argtypes = [C.c_int]
+        L.examg_debug_sys_narrow.restype = C.c_int
     _libs[path] = L
     if path == LIB_PATH:
         _lib = L

@@ -275,6 +275,39 @@ class HipOps:
         check(self.L.examg_prolong_add_cell(C.byref(lc), self.ptr(uc), C.byref(lfine), self.ptr(uf), ivec(begin), ivec(end), self._stream()),
               "examg_prolong_add_cell")
 
+    # -- coupled systems of cell fields -------------------------------------------------------------
+    def _sys(self, lu, u, lf, f, lg, g, ld=None, dst=None):
+        """examg_sys_t of the unknowns u (layout lu), right-hand sides f (lf; None where not read), the n x n coefficient table g (lg; rows
+        of n, None: no term) and the destinations dst (ld)."""
+        n = len(u)
+        y = _lib.SysC()
+        y.n = n
+        for name, l in (("lu", lu), ("lf", lf), ("lg", lg), ("ld", ld if ld is not None else lu)):
+            C.memmove(C.byref(getattr(y, name)), C.byref(l), C.sizeof(_lib.LayoutC))
+        m = min(n, _lib.SYS_MAX)       # an n the library refuses still reaches it
+        for c in range(m):
+            y.u[c] = self.ptr(u[c])
+            y.f[c] = self.ptr(f[c]) if f is not None and f[c] is not None else None
+            y.dst[c] = self.ptr(dst[c]) if dst is not None and dst[c] is not None else None
+            for d in range(m):
+                y.g[c * m + d] = self.ptr(g[c][d]) if g[c][d] is not None else None
+        return y
+
+    def sys_op(self, mode: int, lu, u, lf, f, lg, g, ld, dst, L: Stencil, row_mask: int, begin, end):
+        """dst_c = A u (lib.SYS_APPLY) or f_c - A u (lib.SYS_RESIDUAL) for the rows of row_mask, A = L * I + g (examg_sys_op)."""
+        y, sc = self._sys(lu, u, lf, f, lg, g, ld, dst), L.c_struct(self.ptr)
+        check(self.L.examg_sys_op(int(mode), C.byref(y), C.byref(sc), int(row_mask), ivec(begin), ivec(end), self._stream()), "examg_sys_op")
+
+    def sys_relax(self, lu, u, lf, f, lg, g, L: Stencil, relax: float, colour: int, begin, end):
+        """The local solves of one colour of the red-black smoother of A = L * I + g, in place on u (examg_sys_relax)."""
+        y, sc = self._sys(lu, u, lf, f, lg, g), L.c_struct(self.ptr)
+        check(self.L.examg_sys_relax(C.byref(y), C.byref(sc), float(relax), int(colour), ivec(begin), ivec(end), self._stream()), "examg_sys_relax")
+
+    def pointwise_mul(self, lx, x, ly, y, ld, dst, s: float, begin, end):
+        """dst = (s * x) * y, s = +-1.0 (examg_pointwise_mul)."""
+        check(self.L.examg_pointwise_mul(C.byref(lx), self.ptr(x), C.byref(ly), self.ptr(y), C.byref(ld), self.ptr(dst), float(s), ivec(begin),
+                                         ivec(end), self._stream()), "examg_pointwise_mul")
+
     def scalar_value(self, t) -> float:
         """Host value of a device scalar (the reference's 8-byte D2H copy after a reduction)."""
         return float(t.item())

@@ -667,6 +667,81 @@ int examg_restrict_cell(const examg_layout_t *lfine, const double *rf, const exa
 int examg_prolong_add_cell(const examg_layout_t *lcoarse, const double *uc, const examg_layout_t *lfine, double *uf,
                            const int32_t *begin, const int32_t *end, examg_stream_t stream);
 
+/* ---- Coupled systems of cell-centred unknowns ---------------------------------------------------------------------------
+ * n = 2 or 3 scalar cell fields u_0 .. u_{n-1} coupled at every cell by the operator  A = L * I + G(x):  one constant stencil L
+ * on every component and a point-wise n x n matrix G of coefficient fields (Benchmark/OptFlow2D/2D_FD_OptFlow.exa4: Horn-Schunck
+ * optical flow, `uuSten * u + uvSten * v + alpha * alpha * Laplace * u` with `Stencil uuSten { [0, 0] => IxIx }`; n need not be
+ * the dimensionality).  examg_sys_t names the arrays:
+ *   u[c]        the unknowns, all in layout lu (a cell layout with ghost >= 1 in every dimension)
+ *   f[c]        the right-hand sides, all in layout lf
+ *   g[c * n + d] the coefficient field that multiplies u_d in row c, all in layout lg, read at the cell only; NULL: no such
+ *               term; entries may name one array several times (uvSten and vuSten both hold IxIy): it is loaded once
+ *   dst[c]      the destinations of examg_sys_op, all in layout ld; no dst may be one of the unknowns
+ * Entries of the arrays behind n are ignored.  All four layouts are plain cell layouts (no duplicate layers, no layout
+ * transformation) of one dimensionality (2 or 3) with the same inner sizes; ghost and pad widths may differ.
+ * L: a constant stencil (cfield NULL) whose entries are the centre (required) and axis neighbours at distance 1, each at most
+ * once, in any order; the order is significant.  SCALAR FACTORS ON L are the host's business: `(alpha * alpha) * Laplace` is
+ * stencil arithmetic, the generator folds the factor into the coefficients before it prints the convolution, and so does the
+ * caller here.  (`(alpha ** 2) * (Laplace * u)` multiplies the finished convolution instead; folded into the coefficients it
+ * differs from the generated code in the last bit unless the factor is a power of two.  It is 1 in every reference program.)
+ *
+ * Arithmetic, fp64, no contraction.  conv(L, u_c) = the entries of L folded left to right in declared order: c_0 * u_c(i + o_0),
+ * then + c_k * u_c(i + o_k) (stencil/ir/IR_StencilConvolution.scala:65-68).
+ *   row value    Au_c = (((g[c][0] * u_0) + (g[c][1] * u_1)) [+ (g[c][2] * u_2)]) + conv(L, u_c); NULL terms are skipped, not
+ *                multiplied by zero (a row without coefficient fields is conv(L, u_c) alone)
+ *
+ * examg_sys_op: for every row c of row_mask (bit c) and every cell of [begin,end)
+ *   EXAMG_SYS_APPLY:    dst_c = Au_c                          (`cgTmp1_u = uuSten * cgTmp0_u + uvSten * cgTmp0_v + .. Laplace * cgTmp0_u`)
+ *   EXAMG_SYS_RESIDUAL: dst_c = f_c - Au_c                    (`residual_u = rhs_u - ( uuSten * u + uvSten * v + .. )`)
+ * Rows outside the mask are neither evaluated nor written (the scalar-component programs evaluate one row per loop).  Reads
+ * the unknowns on the box and its one-cell axis shell (ghost cells at the block's faces), coefficients and right-hand sides on
+ * the box; writes the box of dst_c and nothing else.
+ *
+ * examg_sys_relax: one colour of the red-black smoother with the local solve of every cell, in place -- the cells of [begin,end)
+ * with (i0 + i1 + i2) % 2 == colour (the parity of the iterator coordinates, as examg_stencil_op's colour):
+ *     `repeat with { (0 == ((i0 + i1) % 2)), (1 == ((i0 + i1) % 2)), .. loop over u { solve locally relax w { u => .. == rhs_u   v => .. == rhs_v } } .. }`
+ * (baseExt/l4/L4_RepeatLoops.scala; solver/l4/L4_LocalSolve.scala, solver/ir/IR_LocalSolve.scala: the unknowns at the loop's cell
+ * form AVals, every other term goes to fVals).  Per cell
+ *   b_c  = f_c - (the entries of L off the centre folded left to right in declared order over u_c)      [f_c when there are none]
+ *   a_cd = g[c][d], 0.0 for NULL;  a_cc = g[c][c] + L_centre, L_centre alone for NULL
+ *   x solves a x = b:
+ *     n = 2:  det = a00 * a11 - a01 * a10;   x0 = (b0 * a11 - a01 * b1) / det;   x1 = (a00 * b1 - a10 * b0) / det
+ *     n = 3:  the cofactors, each a difference of two products,
+ *               k00 = a11 * a22 - a12 * a21;  k01 = a12 * a20 - a10 * a22;  k02 = a10 * a21 - a11 * a20
+ *               k10 = a02 * a21 - a01 * a22;  k11 = a00 * a22 - a02 * a20;  k12 = a01 * a20 - a00 * a21
+ *               k20 = a01 * a12 - a02 * a11;  k21 = a02 * a10 - a00 * a12;  k22 = a00 * a11 - a01 * a10
+ *             det = (a00 * k00 + a01 * k01) + a02 * k02
+ *             x_i = ((k0i * b0 + k1i * b1) + k2i * b2) / det
+ *   u_c = u_c + relax * (x_c - u_c);  relax == 1.0: u_c = x_c, no arithmetic
+ * The generator emits an inverse times a vector; these are not its bits (its results files carry four digits).  Reads the
+ * neighbours of the other colour and the cell's own values only; writes the colour's cells of the box in u_c and nothing else.
+ *
+ * Both refuse, before anything is launched: n outside 2 .. 3, a layout with duplicate layers (not a cell layout) or under a layout
+ * transformation, layouts of different inner sizes or dimensionality, unknowns without a ghost layer, a stencil field as L, an
+ * entry of L off the axes, further than one cell or repeated, L without a centre entry, a box that leaves an allocation.  An empty
+ * box is a no-op that returns 0.  Rows whose pairs of cells (even array index first) are 16-byte aligned in every argument
+ * (FieldLayout.cell(..., align=2)) are read and written 16 bytes at a time, others 8: the same bits either way. */
+#define EXAMG_SYS_MAX 3
+enum { EXAMG_SYS_APPLY = 0, EXAMG_SYS_RESIDUAL = 1 };
+typedef struct examg_sys {
+  int32_t n;
+  examg_layout_t lu, lf, lg, ld;
+  double *u[EXAMG_SYS_MAX];
+  const double *f[EXAMG_SYS_MAX];
+  const double *g[EXAMG_SYS_MAX * EXAMG_SYS_MAX];
+  double *dst[EXAMG_SYS_MAX];
+} examg_sys_t;
+int examg_sys_op(int mode, const examg_sys_t *sys, const examg_stencil_t *L, uint32_t row_mask, const int32_t *begin, const int32_t *end,
+                 examg_stream_t stream);
+int examg_sys_relax(const examg_sys_t *sys, const examg_stencil_t *L, double relax, int colour, const int32_t *begin, const int32_t *end,
+                    examg_stream_t stream);
+
+/* dst = (s * x) * y over the box, s = +-1.0 exact: the set-up loops `IxIy = Ix * Iy` (s = 1.0) and `rhs_u = -Ix * It` (s = -1.0: the
+ * negation, then the product).  Any localization; every argument through its own layout; plain layouts only; dst may be x or y.
+ * (`It = img1 - img0` needs no entry of its own: examg_axpby with a = 1, b = -1 on a copy of img0 gives x + (-1.0 * y), bitwise x - y.) */
+int examg_pointwise_mul(const examg_layout_t *lx, const double *x, const examg_layout_t *ly, const double *y, const examg_layout_t *ld,
+                        double *dst, double s, const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

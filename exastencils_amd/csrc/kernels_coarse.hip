@@ -238,19 +238,20 @@ struct StencilCGL {
 __global__ void __launch_bounds__(CG_THREADS)
 k_cg_coarse_lds(LayoutDev lu, double *sol, LayoutDev lf, const double *rhs, LayoutDev lr, double *res, LayoutDev lp, double *p,
                 LayoutDev lq, double *ap, StencilCG st, StencilCGL sl, FaceBoxesCG fbr, FaceBoxesCG fbp, FaceBoxesCG fbs, int max_it,
-                double rel_tol, Box box, double *info, int ldx, int ldxy, int ldtot, unsigned flags) {
+                double rel_tol, Box box, double *info, int ldx, int ldxy, int ldtot, int nd, unsigned flags) {
   extern __shared__ double P[];
   __shared__ double sm[CG_SM];
   int turn = 0;
   const int total = (int)box.count();
   const bool from_norm = flags & EXAMG_CG_ALPHA_FROM_NORM, bc = !(flags & EXAMG_CG_NO_BC);
   // halo of the search direction: the boundary planes `apply bc` keeps at zero -- or, for a solver without `apply bc` statements,
-  // whatever those planes hold
+  // whatever those planes hold.  A dimension the layout does not have (one plane, no entry of the stencil leaves it) has no
+  // neighbours in memory: its two halo planes are never read by the mat-vec and stay 0.
   for (int t = threadIdx.x; t < ldtot; t += CG_THREADS) {
     double v = 0.0;
     if (!bc) {
       const int a = t % ldx, rw = t / ldx, b2 = rw % (ldxy / ldx), c = rw / (ldxy / ldx);
-      v = p[lidx_plain(lp, box.b0 - 1 + a, box.b1 - 1 + b2, box.b2 - 1 + c)];
+      if ((nd > 2 || c == 1) && (nd > 1 || b2 == 1)) v = p[lidx_plain(lp, box.b0 - 1 + a, box.b1 - 1 + b2, box.b2 - 1 + c)];
     }
     P[t] = v;
   }
@@ -345,7 +346,7 @@ k_cg_coarse_lds(LayoutDev lu, double *sol, LayoutDev lf, const double *rhs, Layo
       sol[ku[j]] = x[j];
       res[kr[j]] = r[j];
       p[kp[j]] = pv[j];
-      ap[kq[j]] = q[j];
+      if (it > 0) ap[kq[j]] = q[j];   // cgTmp1 is written inside the loop only: with max_it == 0 it keeps what it held
     }
   }
   if (bc) cg_zero_faces(fbs, lu, sol);
@@ -382,6 +383,51 @@ static FaceBoxesCG face_boxes(const examg_layout_t *l, uint32_t face_mask) {
   return fb;
 }
 
+// Which of the two kernels a call takes, decided once from its arguments alone (nothing is launched, no array is touched): the
+// refusals of the entry point, the empty box, and the LDS-resident form where it gives the global-memory form's answer.
+enum CgRoute { CG_REFUSED = -1, CG_EMPTY = 0, CG_GLOBAL = 1, CG_LDS = 2 };
+
+static CgRoute cg_route(const examg_layout_t *lu_, const examg_layout_t *lf_, const examg_layout_t *lr_, const examg_layout_t *lp_,
+                        const examg_layout_t *lq_, const examg_stencil_t *st, uint32_t face_mask, const Box &box, uint32_t flags) {
+  if (flags & ~(EXAMG_CG_ALPHA_FROM_NORM | EXAMG_CG_NO_BC | EXAMG_CG_ZERO_START)) { set_error("examg_cg_coarse_variant: unknown flag"); return CG_REFUSED; }
+  if (lay_split(lu_) || lay_split(lf_) || lay_split(lr_) || lay_split(lp_) || lay_split(lq_)) {
+    set_error("examg_cg_coarse: fields under a layout transformation are not supported by the one-kernel solver (examg_transform_field)");
+    return CG_REFUSED;
+  }
+  const uint32_t all = (1u << (2 * lu_->nd)) - 1;
+  if ((face_mask & all) != all) {
+    set_error("examg_cg_coarse: fused coarse solve needs every face on the physical boundary (single fragment)");
+    return CG_REFUSED;
+  }
+  if ((flags & EXAMG_CG_ZERO_START) && st->cfield) { set_error("examg_cg_coarse_variant: EXAMG_CG_ZERO_START needs constant coefficients"); return CG_REFUSED; }
+  if (box.count() == 0) return CG_EMPTY;
+  if (box.count() > (1 << 22)) { set_error("examg_cg_coarse: box too large for the single-workgroup solver"); return CG_REFUSED; }
+  const int reach = stencil_reach(st);
+  if (!box_inside(lu_, box, reach) || !box_inside(lp_, box, reach) || !box_inside(lf_, box, 0) || !box_inside(lr_, box, 0) ||
+      !box_inside(lq_, box, 0) || (st->cfield && !box_inside(&st->clayout, box, 0))) {
+    set_error("examg_cg_coarse: box leaves an allocation");
+    return CG_REFUSED;
+  }
+  // the mat-vec runs on Solution (residual) and cgTmp0 (A*p): both must share strides
+  const LayoutDev lu = make_layout(lu_), lp = make_layout(lp_);
+  if (lu.s1 != lp.s1 || lu.s2 != lp.s2) { set_error("examg_cg_coarse: Solution and cgTmp0 layouts must agree"); return CG_REFUSED; }
+  // With `apply bc` statements the LDS copy of cgTmp0 has a zero halo.  That is what the mat-vec of the statements reads only when
+  // every neighbour plane of the box is a plane `apply bc` zeroes: the box is the whole interior AND the layout has a duplicate
+  // plane on either side of every dimension.  A layout without one (a cell layout) has ghost cells there, which no statement of
+  // the solver writes: the global-memory form reads what they hold.  Without `apply bc` the halo is loaded from memory.
+  bool whole = true;
+  {
+    const int bb[3] = {box.b0, box.b1, box.b2}, ee[3] = {box.e0, box.e1, box.e2};
+    for (int d = 0; d < lp_->nd; ++d) {
+      whole = whole && bb[d] == lp_->dup_l[d] && ee[d] == lp_->dup_l[d] + lp_->inner[d];
+      if (!(flags & EXAMG_CG_NO_BC)) whole = whole && lp_->dup_l[d] >= 1 && lp_->dup_r[d] >= 1;
+    }
+  }
+  const long long ldx = box.n0() + 2, ldxy = ldx * (box.n1() + 2), ldtot = ldxy * (box.n2() + 2);
+  if (g_cg_lds && whole && !st->cfield && reach <= 1 && box.count() <= CG_PPT * CG_THREADS && ldtot * 8 <= 60 * 1024) return CG_LDS;
+  return CG_GLOBAL;
+}
+
 }  // namespace examg
 
 using namespace examg;
@@ -390,6 +436,14 @@ using namespace examg;
 extern "C" int examg_debug_cg(int lds) {
   examg::g_cg_lds = lds;
   return 0;
+}
+
+// the form examg_cg_coarse_variant takes for these arguments (a CgRoute: -1 refused, with the error set; 0 empty box; 1 global-memory
+// kernel; 2 LDS-resident kernel), under the hook set on this thread; nothing is launched
+extern "C" int examg_debug_cg_route(const examg_layout_t *lu, const examg_layout_t *lf, const examg_layout_t *lr, const examg_layout_t *lp,
+                                    const examg_layout_t *lq, const examg_stencil_t *st, uint32_t face_mask, const int32_t *begin,
+                                    const int32_t *end, uint32_t flags) {
+  return cg_route(lu, lf, lr, lp, lq, st, face_mask, make_box(begin, end), flags);
 }
 #endif
 
@@ -412,44 +466,19 @@ extern "C" int examg_cg_coarse_variant(const examg_layout_t *lu_, double *sol, c
     set_error("examg_cg_coarse: null argument");
     return 1;
   }
-  if (flags & ~(EXAMG_CG_ALPHA_FROM_NORM | EXAMG_CG_NO_BC | EXAMG_CG_ZERO_START)) { set_error("examg_cg_coarse_variant: unknown flag"); return 1; }
-  if (lay_split(lu_) || lay_split(lf_) || lay_split(lr_) || lay_split(lp_) || lay_split(lq_)) {
-    set_error("examg_cg_coarse: fields under a layout transformation are not supported by the one-kernel solver (examg_transform_field)");
-    return 1;
-  }
-  const uint32_t all = (1u << (2 * lu_->nd)) - 1;
-  if ((face_mask & all) != all) {
-    set_error("examg_cg_coarse: fused coarse solve needs every face on the physical boundary (single fragment)");
-    return 1;
-  }
-  if ((flags & EXAMG_CG_ZERO_START) && st->cfield) { set_error("examg_cg_coarse_variant: EXAMG_CG_ZERO_START needs constant coefficients"); return 1; }
   const Box box = make_box(begin, end);
   hipStream_t s = (hipStream_t)stream;
-  if (box.count() == 0) {  // e.g. minLevel 0 on one fragment: CG is a no-op
+  const CgRoute route = cg_route(lu_, lf_, lr_, lp_, lq_, st, face_mask, box, flags);
+  if (route == CG_REFUSED) return 1;
+  if (route == CG_EMPTY) {  // e.g. minLevel 0 on one fragment: CG is a no-op
     if (info) return check_hip(hipMemsetAsync(info, 0, 3 * sizeof(double), s), "examg_cg_coarse memset");
     return 0;
   }
-  if (box.count() > (1 << 22)) { set_error("examg_cg_coarse: box too large for the single-workgroup solver"); return 1; }
-  const int reach = stencil_reach(st);
-  if (!box_inside(lu_, box, reach) || !box_inside(lp_, box, reach) || !box_inside(lf_, box, 0) || !box_inside(lr_, box, 0) ||
-      !box_inside(lq_, box, 0)) {
-    set_error("examg_cg_coarse: box leaves an allocation");
-    return 1;
-  }
-  // the mat-vec runs on Solution (residual) and cgTmp0 (A*p): both must share strides
   const LayoutDev lu = make_layout(lu_), lp = make_layout(lp_);
-  if (lu.s1 != lp.s1 || lu.s2 != lp.s2) { set_error("examg_cg_coarse: Solution and cgTmp0 layouts must agree"); return 1; }
   StencilCG sd;
   const LayoutDev lc = fill_stencil_dev(sd, st, lu);
-  const long long ldx = box.n0() + 2, ldxy = ldx * (box.n1() + 2), ldtot = ldxy * (box.n2() + 2);
-  // the LDS copy of cgTmp0 has a zero halo: right when the box is the whole interior, so that its neighbours are exactly the
-  // boundary planes `apply bc` keeps at zero
-  bool whole = true;
-  {
-    const int bb[3] = {box.b0, box.b1, box.b2}, ee[3] = {box.e0, box.e1, box.e2};
-    for (int d = 0; d < lp_->nd; ++d) whole = whole && bb[d] == lp_->dup_l[d] && ee[d] == lp_->dup_l[d] + lp_->inner[d];
-  }
-  if (g_cg_lds && whole && !st->cfield && reach <= 1 && box.count() <= CG_PPT * CG_THREADS && ldtot * 8 <= 60 * 1024) {
+  if (route == CG_LDS) {
+    const long long ldx = box.n0() + 2, ldxy = ldx * (box.n1() + 2), ldtot = ldxy * (box.n2() + 2);
     StencilCGL sl;
     sl.nent = st->nent;
     for (int k = 0; k < st->nent; ++k) {
@@ -458,7 +487,7 @@ extern "C" int examg_cg_coarse_variant(const examg_layout_t *lu_, double *sol, c
     }
     hipLaunchKernelGGL(k_cg_coarse_lds, dim3(1), dim3(CG_THREADS), (size_t)ldtot * 8, s, lu, sol, make_layout(lf_), rhs, make_layout(lr_), res,
                        lp, p, make_layout(lq_), ap, sd, sl, face_boxes(lr_, face_mask), face_boxes(lp_, face_mask),
-                       face_boxes(lu_, face_mask), max_it, rel_tol, box, info, (int)ldx, (int)ldxy, (int)ldtot, flags);
+                       face_boxes(lu_, face_mask), max_it, rel_tol, box, info, (int)ldx, (int)ldxy, (int)ldtot, (int)lp_->nd, flags);
     EXAMG_CHECK_LAUNCH("k_cg_coarse_lds");
     return 0;
   }

@@ -242,6 +242,11 @@ def load(path=None):
     if hasattr(L, "examg_debug_sys_narrow"):         # debug build only: the 8-byte form of the system kernels
         L.examg_debug_sys_narrow.argtypes = [C.c_int]
         L.examg_debug_sys_narrow.restype = C.c_int
+    if hasattr(L, "examg_debug_cg_route"):           # debug build only: the form of the one-kernel coarse solver, and which one a call takes
+        L.examg_debug_cg.argtypes = [C.c_int]
+        L.examg_debug_cg.restype = C.c_int
+        L.examg_debug_cg_route.argtypes = [lp, lp, lp, lp, lp, sp, C.c_uint32, ip, ip, C.c_uint32]
+        L.examg_debug_cg_route.restype = C.c_int
     _libs[path] = L
     if path == LIB_PATH:
         _lib = L

@@ -466,7 +466,15 @@ int examg_unpack(const examg_layout_t *l, double *x, const double *buf, const in
  * kernel (no host round trips).  Fields in the reference layout.  info: >= 4 doubles in device memory, zeroed by the
  * caller once: info[0] = iterations, info[1] = initial residual, info[2] = final residual of this call; info[3] is
  * incremented when the loop ended at max_it without meeting the tolerance -- where the generated function prints
- * "Maximum number of cgs iterations (max_it) was exceeded" (the host reads the count when it next synchronises). */
+ * "Maximum number of cgs iterations (max_it) was exceeded" (the host reads the count when it next synchronises).  info may be
+ * NULL.  An empty box is a solve of nothing: info[0..2] = 0, nothing else is written.
+ * What is written: sol, res and p on [begin,end); ap on [begin,end) by the first iteration (max_it = 0: ap keeps what it held); the
+ * boundary planes of sol, res and p that `apply bc` zeroes -- per face the duplicate planes of the field's own layout, tangentially
+ * over the ghost range -- `apply bc to Solution` once after the loop, whatever max_it.  Nothing else, and never rhs or the
+ * coefficients.
+ * `apply bc` zeroes duplicate planes.  A layout without a duplicate plane on a face (a cell layout) has ghost cells next to the box
+ * there, which no statement of the solver writes: the mat-vec reads what they hold, as the statements do.  The answer to a call
+ * does not depend on which of the library's two kernels runs it (to the bit). */
 int examg_cg_coarse(const examg_layout_t *lu, double *sol, const examg_layout_t *lf, const double *rhs,
                     const examg_layout_t *lr, double *res, const examg_layout_t *lp, double *p,
                     const examg_layout_t *lq, double *ap, const examg_stencil_t *st, const examg_geom_t *g,

@@ -59,6 +59,9 @@ def _star(coef_of, order, names):
     return Stencil([_AX[n] for n in names[order]], [float(coef_of[n]) for n in names[order]])
 
 
+AXES, star = _AX, _star      # for the other case modules: the offset of an entry name; a star stencil from {name: coefficient}
+
+
 def _distinct_magnitudes(cs):
     m = [abs(c) for c in cs]
     assert len(set(m)) == len(m), "stencil coefficients must be pairwise distinct in magnitude: %r" % (cs,)
@@ -181,6 +184,9 @@ class _Lay:
                 raise IndexError("box %r..%r + %r leaves the allocation in dim %d" % (b, e, off, d))
             sl.append(slice(lo, hi, step))
         return tuple(sl)
+
+
+Lay = _Lay                   # for the other case modules
 
 
 def _dyadic(c):

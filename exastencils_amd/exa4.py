@@ -62,13 +62,14 @@ from .exa4_parser import (Exa4SyntaxError, Exa4Unsupported, FunctionDecl, Parser
                           _colour_cond, _colour_expr, _conjuncts, _const_value, _contains, _find_calls, _has_coord, _lower_cond, _parity_expr, _walk)
 
 from .exa4_systems import Systems  # noqa: E402
+from .exa4_nonlinear import Nonlinear  # noqa: E402
 from .exa4_common import (APPLY, RESIDUAL, SMOOTH, _FN_2D_ONLY, _FN_ANY_DIM, _FN_WITH_PARAM, _N_FN, _Frame, _Return, fn_eval)  # noqa: E402,F401
 from .exa4_builtins import Builtins  # noqa: E402
 from .exa4_fusion import LazyFusions  # noqa: E402
 from .exa4_peepholes import Peepholes  # noqa: E402
 
 
-class Exa4Program(LazyFusions, Peepholes, Builtins, Systems):
+class Exa4Program(LazyFusions, Peepholes, Builtins, Systems, Nonlinear):
     """One ExaSlang-4 program bound to a kernel layer (`ops`: HipOps on the GPU), a block decomposition and a
     communicator.  `run()` executes `Function Application`; printed lines are collected in `self.out`."""
 
@@ -333,7 +334,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Systems):
             raise Exa4Unsupported("cell and node fields mixed in one loop body")
         cell = locs == {"cell"}
         for n in nodes:
-            if cell and n[0] == "sten" and n[1] not in self.transfer and not (n[1] in self._stencil_decls and self._coef_field(n[1]) is not None):
+            if cell and n[0] == "sten" and n[1] not in self.transfer and not (n[1] in self._stencil_decls and (self._coef_field(n[1]) is not None or self._coef_expr(n[1]) is not None)):
                 A = self.stencil(n[1], self._level_of(n[2], fr))
                 if not A.faces_only:
                     raise Exa4Unsupported("stencil %s on a cell field has entries off the axes (edge / corner ghosts are not set)" % n[1])
@@ -459,6 +460,10 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Systems):
                 raise Exa4SyntaxError("stencil %s is not declared on level %d" % (name, lvl))
             if self._coef_field(name) is not None:
                 raise Exa4Unsupported("stencil %s is a point-wise coefficient stencil: it stands only in a system row (P * F) + .. + (L * F)" % name)
+            if self._coef_expr(name) is not None:
+                from .exa4_nonlinear import _FORMS
+
+                raise Exa4Unsupported("coefficient-expression stencil %s outside the forms %s" % (name, _FORMS))
             fr = _Frame(lvl, {})
             offs = [tuple(o) + (0,) * (3 - len(o)) for o, _ in sd.entries]
             s = self.stencils[(name, lvl)] = Stencil(offs, [float(self._eval(e, fr)) for _, e in sd.entries])
@@ -497,6 +502,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Systems):
             return [("const", float(e[1]))]
         if k == "neg":
             return self._compile_point_expr(e[1], lvl, subst) + [("neg", None)]
+        if k == "fld" and subst is not None and "__u" in subst:
+            return [("u", None)]          # the one field access of a coefficient expression: EXAMG_OP_U (exa4_nonlinear.py)
         if k == "id":
             name = e[1]
             if subst is not None and name in subst:
@@ -680,6 +687,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Systems):
         for n in _walk(node):
             if len(n) >= 2 and n[0] == "id" and n[1] in self.globals:
                 reads.add(n[1])
+            elif len(n) == 3 and n[0] == "sten" and n[1] in self._stencil_decls and n[1] not in seen and self._coef_expr(n[1]) is not None:
+                seen.add(n[1])      # a coefficient expression is compiled into every launch: its globals are the recording's
+                reads |= self._globals_below(self._coef_expr(n[1]), seen)[0]
             elif len(n) == 4 and n[0] == "assign" and isinstance(n[2], tuple) and n[2][0] == "id" and n[2][1] in self.globals:
                 assigned.add(n[2][1])
             elif len(n) == 4 and n[0] == "call" and n[1] in self.functions and n[1] not in seen:
@@ -1074,6 +1084,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Systems):
         if lhs[0] != "fld":
             raise Exa4Unsupported("loop body assigns to %s" % lhs[0])
         D, ds = self._field(lhs, fr)
+        if self._names_coef_expr(rhs):
+            raise Exa4Unsupported("semilinear operator (coefficient-expression stencil) %s" % what)
 
         def plain(*fields):
             for X in fields:
@@ -1235,6 +1247,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Systems):
         if (len(body) == 1 and len(boxes) == 1 and colour is None and only is None and where is None and fr.contract is None
                 and self._try_defer(body[0], f, boxes[0], fr)):
             return      # absorbed by a one-pass form later, or run when the next statement could tell the difference
+        if (only is not None or fr.contract is not None) and self._names_coef_expr(("block", list(body))):
+            raise Exa4Unsupported("semilinear operator in a loop with an `only` region or under contraction")
         for st in body:
             if st[0] != "assign":
                 raise Exa4Unsupported("statement %r inside a loop body" % st[0])
@@ -1300,6 +1314,12 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Systems):
             raise Exa4Unsupported("loop body assigns to %s" % lhs[0])
         D, ds = self._field(lhs, fr)
         self.launches += 1
+        if self._names_coef_expr(rhs):
+            try:
+                return self._exec_nonlinear(op, lhs, rhs, D, ds, b, e, colour, fr)
+            except Exa4Unsupported:
+                self.launches -= 1
+                raise
         if op == "=":
             if self._is_scalar(rhs):
                 return ops.set(D.lc, D.data(ds), float(self._eval(rhs, fr)), b, e)

@@ -298,6 +298,7 @@ class Parser:
     def _stencil(self):
         self.expect("Stencil")
         name = self.ident()
+        levels = self.decl_levels() if self.at("@") else None      # `Stencil R@all from default ..` (Testing/NonLinear/FAS_2D_Basic.exa4:30)
         if self.accept("from"):
             self.expect("default")
             kind = self.ident()
@@ -309,7 +310,8 @@ class Parser:
                 raise Exa4Unsupported("default %s on %s with %r" % (kind, loc, interp))
             self.stencils.append(StencilDecl(name, None, [], kind if loc == "Node" else "cell_" + kind))
             return
-        levels = self.decl_levels()
+        if levels is None:
+            levels = self.decl_levels()
         d = StencilDecl(name, levels)
         self.expect("{")
         mapped = []
@@ -919,7 +921,7 @@ def _colour_cond(e, nd: int):
 
 
 def _lower_cond(e):
-    """d if e == (i_d > 0)."""
-    if e[0] == "bin" and e[1] == ">" and e[2][0] == "id" and re.fullmatch(r"i[012]", e[2][1]) and e[3] == ("num", 0):
-        return int(e[2][1][1])
+    """d if e == (i_d > 0); x, y, z are the iterators' other names (Testing/NonLinear/FAS_2D_Basic.exa4:96 `where x > 0 && y > 0`)."""
+    if e[0] == "bin" and e[1] == ">" and e[2][0] == "id" and re.fullmatch(r"i[012]|[xyz]", e[2][1]) and e[3] == ("num", 0):
+        return "xyz".index(e[2][1]) if e[2][1] in "xyz" else int(e[2][1][1])
     return None

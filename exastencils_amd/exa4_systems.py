@@ -24,13 +24,15 @@ class Systems:
         sd = self._stencil_decls.get(name)
         if sd is None or not any(_contains(e, ("fld",)) for _, e in sd.entries):
             return None
+        if not any(e[0] == "fld" for _, e in sd.entries):
+            return None       # expressions over fields only: exa4_nonlinear.py names what it refuses
         if len(sd.entries) != 1:
             raise Exa4Unsupported("stencil %s: a field as an entry of a stencil with more than one entry" % name)
         off, e = sd.entries[0]
         if any(o != 0 for o in off):
             raise Exa4Unsupported("stencil %s: a field as an entry off the centre" % name)
         if e[0] != "fld":
-            raise Exa4Unsupported("stencil %s: the centre entry must be one field access" % name)
+            return None       # an expression over a field: a coefficient-expression stencil (exa4_nonlinear.py)
         return e
 
     # -- system rows ----------------------------------------------------------------------------------------------------------

@@ -74,6 +74,34 @@ class ExprC(C.Structure):
         return e
 
 
+MAX_NL_EXPR = 32
+NL_STACK = 8
+NL_APPLY, NL_RESIDUAL, NL_ADD = 0, 1, 2
+NL_OPS = dict(OPS, u=22)
+for _pos in ("x", "y", "z"):      # a program over a field value has no node position
+    del NL_OPS[_pos]
+
+
+class NlExprC(C.Structure):
+    """examg_nlexpr_t: a postfix program over the value of a field at the point (include/examg.h); `u` pushes that value."""
+    _fields_ = [("n", C.c_int32), ("op", C.c_int32 * MAX_NL_EXPR), ("c", C.c_double * MAX_NL_EXPR)]
+
+    @staticmethod
+    def from_program(prog):
+        """prog: list of (opcode name, constant or None)."""
+        if not 1 <= len(prog) <= MAX_NL_EXPR:
+            raise ValueError("point program with %d instructions (limit %d)" % (len(prog), MAX_NL_EXPR))
+        e = NlExprC()
+        e.n = len(prog)
+        for i, (name, c) in enumerate(prog):
+            if name not in NL_OPS:
+                raise ValueError("point program with the instruction %r" % name)
+            e.op[i] = NL_OPS[name]
+            e.c[i] = float(c) if c is not None else 0.0
+        e.program = list(prog)
+        return e
+
+
 class ExamgError(RuntimeError):
     pass
 
@@ -99,6 +127,7 @@ SYMBOLS = [
     "examg_prolong_add_cell",
     "examg_stencil_op_coloured", "examg_mcgs_sweep", "examg_mcgs_one_pass_eligible",
     "examg_sys_op", "examg_sys_relax", "examg_pointwise_mul",
+    "examg_nl_op", "examg_nl_smooth",
 ]
 
 COMM_ID_BYTES = 128
@@ -225,6 +254,9 @@ def load(path=None):
     L.examg_sys_op.argtypes = [C.c_int, yp, sp, C.c_uint32, ip, ip, vp]
     L.examg_sys_relax.argtypes = [yp, sp, C.c_double, C.c_int, ip, ip, vp]
     L.examg_pointwise_mul.argtypes = [lp, vp, lp, vp, lp, vp, C.c_double, ip, ip, vp]
+    np_ = C.POINTER(NlExprC)
+    L.examg_nl_op.argtypes = [C.c_int, lp, vp, lp, vp, lp, vp, lp, vp, sp, np_, ip, ip, vp]
+    L.examg_nl_smooth.argtypes = [lp, vp, lp, vp, lp, vp, sp, np_, np_, C.c_double, C.c_int, ip, ip, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("examg_version", "examg_last_error", "examg_device_count", "examg_reduce_work_bytes", "examg_exchange_workspace_bytes",
@@ -239,6 +271,9 @@ def load(path=None):
     if hasattr(L, "examg_debug_mcgs_per_colour"):    # debug build only: examg_mcgs_sweep as its colour loops
         L.examg_debug_mcgs_per_colour.argtypes = [C.c_int]
         L.examg_debug_mcgs_per_colour.restype = C.c_int
+    if hasattr(L, "examg_debug_nl_gather_only"):     # debug build only: star stencils of the semilinear kernels on the gather kernel
+        L.examg_debug_nl_gather_only.argtypes = [C.c_int]
+        L.examg_debug_nl_gather_only.restype = C.c_int
     if hasattr(L, "examg_debug_sys_narrow"):         # debug build only: the 8-byte form of the system kernels
         L.examg_debug_sys_narrow.argtypes = [C.c_int]
         L.examg_debug_sys_narrow.restype = C.c_int

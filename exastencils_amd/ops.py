@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 
 from . import lib as _lib
 from .field import Colouring, Stencil, fn_expr  # noqa: F401  (Colouring: the value type of the coloured entry points)
-from .lib import ExamgError, check, ivec
+from .lib import NL_ADD, NL_APPLY, NL_RESIDUAL, ExamgError, check, ivec  # noqa: F401  (NL_*: the modes of nl_op)
 
 
 class HipOps:
@@ -307,6 +307,20 @@ class HipOps:
         """dst = (s * x) * y, s = +-1.0 (examg_pointwise_mul)."""
         check(self.L.examg_pointwise_mul(C.byref(lx), self.ptr(x), C.byref(ly), self.ptr(y), C.byref(ld), self.ptr(dst), float(s), ivec(begin),
                                          ivec(end), self._stream()), "examg_pointwise_mul")
+
+    # -- semilinear operators A * u + c(q) . u -------------------------------------------------------
+    def nl_op(self, mode: int, lu, u, lq, q, lf, rhs, ld, dst, st: Stencil, c, begin, end):
+        """dst = N (lib.NL_APPLY), rhs - N (lib.NL_RESIDUAL) or dst + N (lib.NL_ADD), N = st * u + c(q) . u; c: lib.NlExprC (examg_nl_op)."""
+        sc = st.c_struct(self.ptr)
+        check(self.L.examg_nl_op(int(mode), C.byref(lu), self.ptr(u), C.byref(lq), self.ptr(q), C.byref(lf) if lf is not None else None,
+                                 self.ptr(rhs) if rhs is not None else None, C.byref(ld), self.ptr(dst), C.byref(sc), C.byref(c), ivec(begin),
+                                 ivec(end), self._stream()), "examg_nl_op")
+
+    def nl_smooth(self, lu, u_in, ld, u_out, lf, rhs, st: Stencil, c, d, w: float, colour: int, begin, end):
+        """u_out = u + w * ((rhs - (st * u + c(u) . u)) / (diag(st) + d(u))): colour -1 out of place, 0 / 1 in place (examg_nl_smooth)."""
+        sc = st.c_struct(self.ptr)
+        check(self.L.examg_nl_smooth(C.byref(lu), self.ptr(u_in), C.byref(ld), self.ptr(u_out), C.byref(lf), self.ptr(rhs), C.byref(sc),
+                                     C.byref(c), C.byref(d), float(w), int(colour), ivec(begin), ivec(end), self._stream()), "examg_nl_smooth")
 
     def scalar_value(self, t) -> float:
         """Host value of a device scalar (the reference's 8-byte D2H copy after a reduction)."""

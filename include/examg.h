@@ -750,6 +750,55 @@ int examg_sys_relax(const examg_sys_t *sys, const examg_stencil_t *L, double rel
 int examg_pointwise_mul(const examg_layout_t *lx, const double *x, const examg_layout_t *ly, const double *y, const examg_layout_t *ld,
                         double *dst, double s, const int32_t *begin, const int32_t *end, examg_stream_t stream);
 
+/* ---- Semilinear operators: N(q; u) = A * u + c(q) . u ---------------------------------------------------------------------
+ * A a constant stencil (cfield NULL; any entry list, 2-D or 3-D), c a point expression over the value of a node field q AT THE POINT:
+ * `Stencil gamSten { [0, 0] => gam * exp ( Solution<active>@current ) }`, `Laplace * Solution + gamSten * Solution`
+ * (Testing/NonLinear/FAS_2D_Basic.exa4:26-28, 82, 91, 128: -Laplace u + gam u e^u = f with a full-approximation-scheme V-cycle).  q and u
+ * are separate arguments: `gamSten@coarser * Approximation@coarser` reads Solution inside the stencil and multiplies Approximation.
+ * The expression travels as a postfix program like every analytic expression of the library, in a compact type: the kernels take
+ * the stencil and up to two programs by value as kernel arguments, and examg_expr_t (3 KB) would not fit beside them.
+ * EXAMG_OP_U pushes the value of q at the point; the position ops EXAMG_OP_X/Y/Z are refused in these programs, and EXAMG_OP_U is
+ * refused by every entry point that takes an examg_expr_t.  The operand stack of a program may be at most EXAMG_NL_STACK deep (it
+ * lives in registers).
+ *
+ * Arithmetic, fp64, no contraction, per point of the box:
+ *   conv = the entries of A folded left to right in declared order over u (c_0 * u(i + o_0), then + c_k * u(i + o_k))
+ *   N    = conv + (c(q(i)) * u(i)),      c evaluated in the order of the program
+ * examg_nl_op:
+ *   EXAMG_NL_APPLY    dst = N                      (`D = A * U + S * U`)
+ *   EXAMG_NL_RESIDUAL dst = rhs - N                (`Residual = RHS - ( Laplace * Solution + gamSten * Solution )`)
+ *   EXAMG_NL_ADD      dst = dst + N                (`RHS@coarser += Laplace@coarser * Approximation@coarser + gamSten@coarser * Approximation@coarser`)
+ * examg_nl_smooth: one damped Newton step per point on the diagonal of the Jacobian, q = u:
+ *   u_out = u + w * ((rhs - N) / (diag(A) + d(u(i))))         diag(A) = st->coef[st->diag], d a second program over u(i)
+ *   (`Solution<next> = Solution<active> + 0.8 * ( ( RHS - ( Laplace * Solution<active> + gamSten * Solution<active> ) )
+ *                      / ( diag ( Laplace ) + gam * ( 1.0 + Solution<active> ) * exp ( Solution<active> ) ) )`, ...exa4:81-83)
+ *   colour = -1: all points, out of place (u_out != u_in: Jacobi); colour 0 / 1: the points with (i0 + i1 [+ i2]) % 2 == colour, in place
+ *   (u_out == u_in: a nonlinear red-black Gauss-Seidel half sweep), and only for stencils the parity decouples (every entry off the
+ *   centre has an odd offset sum: star stencils) -- on any other stencil the in-place loop depends on its order.
+ * Every argument is indexed through its own layout (u: lu, q: lq, rhs: lf, dst / u_out: ld); only the points of the box (of the
+ * colour) are written, in dst / u_out alone.  examg_nl_op: dst must not be u; q may be any of the arrays.  rhs / lf may be NULL
+ * for EXAMG_NL_APPLY and EXAMG_NL_ADD.
+ * Both refuse, before anything is launched: a stencil field, a stencil without a centre entry (st->diag must name the (0,0,0)
+ * entry), layouts under a layout transformation (colour split), cell layouts (no duplicate layers), layouts that are not 2-D or
+ * 3-D, a box that leaves an allocation (u: grown by the stencil's reach), a program that is empty, longer than EXAMG_MAX_NL_EXPR,
+ * deeper than EXAMG_NL_STACK, breaks the stack discipline or holds an unknown or a position opcode.  An empty box is a no-op that
+ * returns 0.  Nothing is allocated; the launches are capturable. */
+#define EXAMG_OP_U 22
+#define EXAMG_MAX_NL_EXPR 32
+#define EXAMG_NL_STACK 8
+typedef struct {
+  int32_t n;
+  int32_t op[EXAMG_MAX_NL_EXPR];
+  double c[EXAMG_MAX_NL_EXPR];
+} examg_nlexpr_t;
+enum { EXAMG_NL_APPLY = 0, EXAMG_NL_RESIDUAL = 1, EXAMG_NL_ADD = 2 };
+int examg_nl_op(int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lq, const double *q, const examg_layout_t *lf,
+                const double *rhs, const examg_layout_t *ld, double *dst, const examg_stencil_t *st, const examg_nlexpr_t *c,
+                const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_nl_smooth(const examg_layout_t *lu, const double *u_in, const examg_layout_t *ld, double *u_out, const examg_layout_t *lf,
+                    const double *rhs, const examg_stencil_t *st, const examg_nlexpr_t *c, const examg_nlexpr_t *d, double w, int colour,
+                    const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,9 @@ assignments, `loop over f [only dup [..] on boundary] [where c] [with reduction 
 `color with`, `return`, level scopes `@(...) { }` (:653-667), declaration level lists `@all`, `@(a to b)`, `@(a, b)`,
 `@(a and b)`, `@(all but x)`, `coarsest + 1`, and access levels `@current|coarser|finer|finest|coarsest|<n>`.
 
-Loop bodies recognised (anything else raises Exa4Unsupported -- nothing is silently approximated):
+Loop bodies recognised (anything else raises Exa4Unsupported -- nothing is silently approximated); the assignments among them by the
+one recogniser of exa4_statements.py (`_recognise_assign` -> LoopStmt) and issued by its launcher (`_launch`, `_launch_coloured`), the
+whole-loop forms (reductions, stencil-field initialisation, builtins, `solve locally`) by executors of their own:
   F = c | F = G | F = analytic(x,y,z) | F += a*G | F -= a*G | F = G + b*F            examg_set/fill_fn/axpby
   R = RHS - A*U | D = A*U                                                            examg_residual / stencil_op(APPLY)
   U<next> = U<active> + w(diag A) * (RHS - A*U<active>)                              examg_jacobi
@@ -63,13 +65,14 @@ from .exa4_parser import (Exa4SyntaxError, Exa4Unsupported, FunctionDecl, Parser
 
 from .exa4_systems import Systems  # noqa: E402
 from .exa4_nonlinear import Nonlinear  # noqa: E402
+from .exa4_statements import Statements  # noqa: E402
 from .exa4_common import (APPLY, RESIDUAL, SMOOTH, _FN_2D_ONLY, _FN_ANY_DIM, _FN_WITH_PARAM, _N_FN, _Frame, _Return, fn_eval)  # noqa: E402,F401
 from .exa4_builtins import Builtins  # noqa: E402
 from .exa4_fusion import LazyFusions  # noqa: E402
 from .exa4_peepholes import Peepholes  # noqa: E402
 
 
-class Exa4Program(LazyFusions, Peepholes, Builtins, Systems, Nonlinear):
+class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonlinear):
     """One ExaSlang-4 program bound to a kernel layer (`ops`: HipOps on the GPU), a block decomposition and a
     communicator.  `run()` executes `Function Application`; printed lines are collected in `self.out`."""
 
@@ -1078,56 +1081,15 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Systems, Nonlinear):
                 self._exec_point_assign_multicolour(st, b, e, fr)
 
     def _exec_point_assign_multicolour(self, st, b, e, fr: _Frame):
-        op, lhs, rhs = st[1], st[2], st[3]
-        col = fr.mcolour
         what = "under a multi-colouring (color with several expressions)"
-        if lhs[0] != "fld":
-            raise Exa4Unsupported("loop body assigns to %s" % lhs[0])
-        D, ds = self._field(lhs, fr)
-        if self._names_coef_expr(rhs):
+        if st[2][0] != "fld":
+            self._recognise_assign(st, fr)      # names what the loop assigns to
+        if self._names_coef_expr(st[3]):
             raise Exa4Unsupported("semilinear operator (coefficient-expression stencil) %s" % what)
-
-        def plain(*fields):
-            for X in fields:
-                if X.layout.transform:
-                    raise Exa4Unsupported("colour-split field %s %s" % (X.name, what))
-
-        def in_place_ok(kind, U, us, A):
-            # a loop that reads the array it writes: only where no point of the colour is a neighbour of another one
-            if D is U and ds == us and not col.decouples(A.offsets):
-                raise Exa4Unsupported("in-place %s %s: the colouring does not decouple the stencil (two points of one colour are "
-                                      "neighbours: the generated loop depends on its order)" % (kind, what))
-
-        m = self._match_smoother(st, fr) if op in ("=", "+=") else None
-        if m is None and op in ("=", "+="):
-            # _match_smoother declines fields under a layout transformation: name the construct instead of "not a kernel"
-            for n in _walk(st):
-                if n and n[0] == "fld" and isinstance(n[1], str) and self._field(n, fr)[0].layout.transform:
-                    raise Exa4Unsupported("colour-split field %s %s" % (n[1], what))
-        if m is not None:
-            D, ds, U, us, F, fs, A, wv = m
-            plain(D, U, F)
-            in_place_ok("smoother", U, us, A)
-            self.launches += 1
-            return self.ops.stencil_op_coloured(SMOOTH, U.lc, U.data(us), F.lc, F.data(fs), D.lc, D.data(ds), A, wv, col, b, e)
-        if op == "=":
-            r = self._residual_form(rhs, fr)
-            if r is not None:
-                F, fs = self._field(r[0], fr)
-                U, us = self._field(r[2], fr)
-                plain(D, U, F)
-                in_place_ok("residual loop", U, us, r[1])
-                self.launches += 1
-                return self.ops.stencil_op_coloured(RESIDUAL, U.lc, U.data(us), F.lc, F.data(fs), D.lc, D.data(ds), r[1], 0.0, col, b, e)
-            a = self._sten_times_field(rhs, fr)
-            if a is not None and a[1] == "stencil" and a[0] == 1.0:
-                X, xs = self._field(a[4], fr)
-                plain(D, X)
-                in_place_ok("stencil application", X, xs, a[2])
-                self.launches += 1
-                return self.ops.stencil_op_coloured(APPLY, X.lc, X.data(xs), None, None, D.lc, D.data(ds), a[2], 0.0, col, b, e)
-        raise Exa4Unsupported("loop body statement %s %s ... %s: only stencil loops (A * u, f - A * u, u + w * (f - A * u)) have a coloured kernel"
-                              % (lhs[1], op, what))
+        k = self._recognise_or_none(st, fr)     # whatever the recogniser refuses has no coloured kernel either
+        if k is None or not self._launch_coloured(k, b, e, fr.mcolour):
+            raise Exa4Unsupported("loop body statement %s %s ... %s: only stencil loops (A * u, f - A * u, u + w * (f - A * u)) have a coloured kernel"
+                                  % (st[2][1], st[1], what))
 
     def _apply_bc(self, f: Field, slot: int):
         if f.layout.is_cell:
@@ -1257,159 +1219,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Systems, Nonlinear):
                 self._bc_epoch[(tf.name, tf.level)] = self._bc_epoch.get((tf.name, tf.level), 0) + 1
                 self._bc_valid -= {(tf.name, tf.level, sl) for sl in range(tf.num_slots)}
             for b, e in boxes:
-                self._exec_point_assign(st, b, e, colour, fr)
-
-    # pattern helpers ---------------------------------------------------------------------------------------------------
-    def _is_scalar(self, e) -> bool:
-        return not _contains(e, ("fld", "sten", "sentry")) and not _has_coord(e, self.functions)
-
-    def _same_access(self, a, b, fr: _Frame) -> bool:
-        if a[0] != "fld" or b[0] != "fld":
-            return False
-        fa, sa = self._field(a, fr)
-        fb, sb = self._field(b, fr)
-        return fa is fb and sa == sb
-
-    def _sten_times_field(self, e, fr: _Frame):
-        """(scale, kind, stencil-or-name, stencil level, field expr) for `[s *] S * F`."""
-        if e[0] != "bin" or e[1] != "*" or e[3][0] != "fld":
-            return None
-        s, scale = e[2], 1.0
-        if s[0] == "bin" and s[1] == "*" and s[3][0] == "sten" and self._is_scalar(s[2]):
-            scale, s = float(self._eval(s[2], fr)), s[3]
-        if s[0] != "sten":
-            return None
-        if s[1] in self.transfer:
-            return scale, self.transfer[s[1]], s[1], None, e[3]
-        return scale, "stencil", self.stencil(s[1], self._level_of(s[2], fr)), None, e[3]
-
-    def _residual_form(self, e, fr: _Frame):
-        """(F, A, U) for `F - A * U`."""
-        if e[0] != "bin" or e[1] != "-" or e[2][0] != "fld":
-            return None
-        m = self._sten_times_field(e[3], fr)
-        if m is None or m[1] != "stencil" or m[0] != 1.0:
-            return None
-        return e[2], m[2], m[4]
-
-    def _smoother_weight(self, w, A: Stencil, fr: _Frame):
-        """(omega, stencil as the kernel needs it): a stencil field carries the FORM of the weight -- the kernels evaluate per point
-        what the statement says, `(1.0 / diag(A)) * omega` (Testing/SISC/3D_VarCoeff.exa4:145) or `omega / diag(A)`
-        (Testing/PolyExpl/RBGS3Dvc.exa4:52); the two round differently."""
-        if A.cfield is None:
-            return float(self._eval(w, fr)), A
-        if (w[0] == "bin" and w[1] == "*" and w[2][0] == "bin" and w[2][1] == "/" and w[2][2] == ("num", 1.0)
-                and w[2][3][0] == "call" and w[2][3][1] == "diag" and self._is_scalar(w[3])):
-            return float(self._eval(w[3], fr)), A
-        if w[0] == "bin" and w[1] == "/" and w[3][0] == "call" and w[3][1] == "diag" and self._is_scalar(w[2]):
-            import dataclasses
-
-            return float(self._eval(w[2], fr)), dataclasses.replace(A, wform=1)
-        raise Exa4Unsupported("smoother weight on a stencil field must read ((1.0 / diag(A)) * omega) or (omega / diag(A))")
-
-    def _exec_point_assign(self, st, b, e, colour, fr: _Frame):
-        op, lhs, rhs = st[1], st[2], st[3]
-        ops = self.ops
-        if lhs[0] != "fld":
-            raise Exa4Unsupported("loop body assigns to %s" % lhs[0])
-        D, ds = self._field(lhs, fr)
-        self.launches += 1
-        if self._names_coef_expr(rhs):
-            try:
-                return self._exec_nonlinear(op, lhs, rhs, D, ds, b, e, colour, fr)
-            except Exa4Unsupported:
-                self.launches -= 1
-                raise
-        if op == "=":
-            if self._is_scalar(rhs):
-                return ops.set(D.lc, D.data(ds), float(self._eval(rhs, fr)), b, e)
-            if not _contains(rhs, ("fld", "sten", "sentry")) and D.layout.is_cell:
-                return ops.fill_expr_cell(D.lc, D.data(ds), self.domain.geom(D.level), self._cell_program(rhs, D.level), b, e)
-            if not _contains(rhs, ("fld", "sten", "sentry")):
-                fn, par = self._analytic(rhs, D.level)
-                if isinstance(fn, int):
-                    return ops.fill_fn(D.lc, D.data(ds), self.domain.geom(D.level), fn, par, b, e)
-                return ops.fill_expr(D.lc, D.data(ds), self.domain.geom(D.level), fn, b, e)
-            if rhs[0] == "fld":
-                X, xs = self._field(rhs, fr)
-                return ops.axpby(X.lc, X.data(xs), D.lc, D.data(ds), 1.0, 0.0, b, e)
-            if self._exec_system_assign(D, ds, rhs, b, e, colour, fr) or (colour is None and self._exec_pointwise(D, ds, rhs, b, e, fr)):
-                return
-            r = self._residual_form(rhs, fr)
-            if r is not None:
-                F, fs = self._field(r[0], fr)
-                U, us = self._field(r[2], fr)
-                return ops.stencil_op(RESIDUAL, U.lc, U.data(us), F.lc, F.data(fs), D.lc, D.data(ds), r[1], 0.0, -1, b, e)
-            m = self._sten_times_field(rhs, fr)
-            if m is not None:
-                X, xs = self._field(m[4], fr)
-                if m[1] in ("restriction", "cell_restriction") and (m[1] == "cell_restriction") != (X.layout.is_cell and D.layout.is_cell):
-                    raise Exa4Unsupported("%s restriction %s between %s and %s fields" % ("cell" if m[1][0] == "c" else "node", m[2],
-                                                                                          X.layout.localization, D.layout.localization))
-                if m[1] == "cell_restriction":
-                    if X.level != D.level + 1:
-                        raise Exa4Unsupported("restriction between levels %d and %d" % (X.level, D.level))
-                    return ops.restrict_cell(X.lc, X.data(xs), D.lc, D.data(ds), m[0], b, e)
-                if m[1] == "restriction":
-                    if X.level != D.level + 1:
-                        raise Exa4Unsupported("restriction between levels %d and %d" % (X.level, D.level))
-                    return ops.restrict(X.lc, X.data(xs), D.lc, D.data(ds), m[0], b, e)
-                if m[1] == "stencil" and m[0] == 1.0:
-                    return ops.stencil_op(APPLY, X.lc, X.data(xs), None, None, D.lc, D.data(ds), m[2], 0.0, -1, b, e)
-            if rhs[0] == "bin" and rhs[1] == "+" and rhs[2][0] == "fld":
-                # U_src + w * (F - A * U_src)   |   G + beta * D
-                t = rhs[3]
-                if t[0] == "bin" and t[1] == "*":
-                    r = self._residual_form(t[3], fr)
-                    if r is not None and self._same_access(rhs[2], r[2], fr):
-                        return self._smooth(D, ds, rhs[2], t[2], r, b, e, colour, fr)
-                    if t[3][0] == "fld" and self._same_access(lhs, t[3], fr) and self._is_scalar(t[2]):
-                        X, xs = self._field(rhs[2], fr)
-                        return ops.axpby(X.lc, X.data(xs), D.lc, D.data(ds), 1.0, float(self._eval(t[2], fr)), b, e)
-        elif op in ("+=", "-="):
-            sign = 1.0 if op == "+=" else -1.0
-            if self._is_scalar(rhs):     # F += s | F -= s  (x + (-s) is exactly x - s)
-                return ops.add_scalar(D.lc, D.data(ds), sign * float(self._eval(rhs, fr)), b, e)
-            if rhs[0] == "fld":          # x += y | x -= y  (y + (-1.0) * x is exactly y - x)
-                X, xs = self._field(rhs, fr)
-                return ops.axpby(X.lc, X.data(xs), D.lc, D.data(ds), sign, 1.0, b, e)
-            if rhs[0] == "bin" and rhs[1] == "*":
-                if rhs[3][0] == "fld" and self._is_scalar(rhs[2]):
-                    X, xs = self._field(rhs[3], fr)
-                    return ops.axpby(X.lc, X.data(xs), D.lc, D.data(ds), sign * float(self._eval(rhs[2], fr)), 1.0, b, e)
-                r = self._residual_form(rhs[3], fr)
-                if r is not None and op == "+=" and self._same_access(lhs, r[2], fr):
-                    return self._smooth(D, ds, lhs, rhs[2], r, b, e, colour, fr)
-                m = self._sten_times_field(rhs, fr)
-                if m is not None and m[1] in ("prolongation", "cell_prolongation") and op == "+=" and m[0] == 1.0:
-                    X, xs = self._field(m[4], fr)
-                    if (m[1] == "cell_prolongation") != (X.layout.is_cell and D.layout.is_cell):
-                        raise Exa4Unsupported("%s prolongation %s between %s and %s fields" % ("cell" if m[1][0] == "c" else "node", m[2],
-                                                                                               X.layout.localization, D.layout.localization))
-                if m is not None and m[1] == "cell_prolongation" and op == "+=" and m[0] == 1.0:
-                    if X.level != D.level - 1:
-                        raise Exa4Unsupported("prolongation between levels %d and %d" % (X.level, D.level))
-                    return ops.prolong_add_cell(X.lc, X.data(xs), D.lc, D.data(ds), b, e)
-                if m is not None and m[1] == "prolongation" and op == "+=" and m[0] == 1.0:
-                    X, xs = self._field(m[4], fr)
-                    if X.level != D.level - 1:
-                        raise Exa4Unsupported("prolongation between levels %d and %d" % (X.level, D.level))
-                    return ops.prolong_add(X.lc, X.data(xs), D.lc, D.data(ds), b, e)
-        self.launches -= 1
-        raise Exa4Unsupported("loop body statement is none of the recognised kernels: %s %s ..." % (lhs[1], op))
-
-    def _smooth(self, D: Field, ds: int, src, w, r, b, e, colour, fr: _Frame):
-        F, fs = self._field(r[0], fr)
-        U, us = self._field(src, fr)
-        A = r[1]
-        wv, A = self._smoother_weight(w, A, fr)
-        in_place = D is U and ds == us
-        if in_place and colour is None:
-            raise Exa4Unsupported("in-place smoother update without colouring (lexicographic Gauss-Seidel)")
-        if not in_place and colour is not None:
-            raise Exa4Unsupported("coloured update into another slot")
-        return self.ops.stencil_op(SMOOTH, U.lc, U.data(us), F.lc, F.data(fs), D.lc, D.data(ds), A, wv,
-                                   -1 if colour is None else colour, b, e)
+                self._launch(self._recognise_assign(st, fr, colour), b, e, colour)
 
     def _exec_reduction(self, f: Field, boxes, reduction, body, fr: _Frame):
         op, var = reduction

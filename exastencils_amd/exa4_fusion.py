@@ -9,6 +9,10 @@ A loop that one of the one-pass kernels can absorb is not launched when the inte
   Solution@coarser = 0.0                   pending until  the red-black sweep that follows        -> examg_rbgs_sweep_fused_zero
   Solution += Prolongation * Solution@coarser  pending until  the red-black sweep that follows   -> examg_rbgs_sweep_fused_prolong
 
+Which of the three a loop is, `_try_defer` reads off the record of the one recogniser (exa4_statements.py: LoopStmt) and adds its own
+conditions; the pending loop IS that record plus its box (`Pending`), so running it after all is the launcher's `_launch` of the very
+statement (`_flush_pending`), and the restriction that consumes a residual is the recogniser's `restrict`.
+
 Statements in between pass through if they cannot observe the difference (`apply bc` of the pending field, scalar statements,
 function calls -- their bodies are gated statement by statement -- and `communicate` on a block without neighbours); anything else
 makes the pending loop run first.  The first two forms never store the residual, so they also need a proof that nothing reads it:
@@ -21,16 +25,27 @@ Reference: what the generator would reach with loop fusion across inlined functi
 IR_GeneralSimplify, polyhedron/ -- schedule-level fusion); there is no counterpart of the never-stored residual in the reference."""
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional, Tuple
 
+from .exa4_statements import LoopStmt
+
 READ, WRITTEN, NEITHER = "read", "written", "neither"
+
+
+@dataclass(frozen=True)
+class Pending:
+    """A loop that was not launched where it stands: what it is, and its box."""
+    stmt: LoopStmt
+    b: list
+    e: list
 
 
 class LazyFusions:
     """Mixin of Exa4Program: continuation stack, pending loops, liveness."""
 
     def _lazy_init(self):
-        self._pending: Optional[dict] = None
+        self._pending: Optional[Pending] = None
         self._cont: list = []                 # active statement lists, innermost last: [body, index, frame, is_loop, is_function]
         self._summary: dict = {}
         self.fusions = {"residual_restrict": 0, "residual_norm": 0, "zero_start": 0, "folded_correction": 0}
@@ -44,70 +59,54 @@ class LazyFusions:
         return bool(self.fuse and self.domain.world_size == 1 and not any(self.domain.periodic))
 
     def _try_defer(self, st, target, box, fr) -> bool:
-        """Keep the single-statement loop `st` over the whole box of `target` pending if it is one of the three absorbable kinds."""
+        """Keep the single-statement loop `st` over the whole box of `target` pending if the recogniser (exa4_statements.py) says it
+        is one of the three absorbable kinds: `set` to 0.0, `residual`, `prolong_add` (from the level below: the recogniser's check)."""
         if not self._lazy_enabled() or self._pending is not None or st[0] != "assign" or st[2][0] != "fld":
             return False
-        op, lhs, rhs = st[1], st[2], st[3]
-        D, ds = self._field(lhs, fr)
+        D, ds = self._field(st[2], fr)
         if D is not target or D.num_slots != 1 or D.layout.transform or D.layout.is_cell or self._touches_cell([st]):
             return False        # cell fields are never deferred: no one-pass form has their ghost updates
         b, e = box
         fb, fe = self.domain.loop_bounds(D.layout)
         if list(b) != list(fb) or list(e) != list(fe):
             return False
-        if op == "=":
-            if self._is_scalar(rhs):
-                if float(self._eval(rhs, fr)) != 0.0 or D.bc_fn != 0 or (D.name, D.level, ds) not in self._bc_valid or \
-                        not hasattr(self.ops, "rbgs_sweep_fused_zero") or D.layout.inner[0] < self.fuse_min_row or self.nd != 3:
-                    return False
-                self._pending = dict(kind="zero", D=D, ds=ds, b=b, e=e)
-                return True
-            r = self._residual_form(rhs, fr)
-            if r is None or not hasattr(self.ops, "residual_restrict") or self.nd != 3:
+        k = self._recognise_or_none(st, fr)
+        if k is None:
+            return False
+        if k.kind == "set":
+            if k.s != 0.0 or D.bc_fn != 0 or (D.name, D.level, ds) not in self._bc_valid or \
+                    not hasattr(self.ops, "rbgs_sweep_fused_zero") or D.layout.inner[0] < self.fuse_min_row or self.nd != 3:
                 return False
-            F, fs = self._field(r[0], fr)
-            U, us = self._field(r[2], fr)
-            A = r[1]
-            if U.layout.transform or F.layout.transform:
+        elif k.kind == "residual":
+            if not hasattr(self.ops, "residual_restrict") or self.nd != 3:
                 return False
-            if U is D or F is D or not self._canonical7(A, self.nd) or D.layout.inner[0] < self.fuse_min_row:
+            if k.U.layout.transform or k.F.layout.transform:
                 return False
-            self._pending = dict(kind="residual", D=D, ds=ds, U=U, us=us, F=F, fs=fs, A=A, b=b, e=e)
-            return True
-        if op == "+=" and rhs[0] == "bin" and rhs[1] == "*":
-            m = self._sten_times_field(rhs, fr)
-            if m is None or m[1] != "prolongation" or m[0] != 1.0 or not hasattr(self.ops, "rbgs_sweep_fused_prolong") or self.nd != 3:
+            if k.U is D or k.F is D or not self._canonical7(k.A, self.nd) or D.layout.inner[0] < self.fuse_min_row:
                 return False
-            X, xs = self._field(m[4], fr)
-            if X.layout.transform:
+        elif k.kind == "prolong_add":
+            if not hasattr(self.ops, "rbgs_sweep_fused_prolong") or self.nd != 3:
+                return False
+            if k.U.layout.transform:
                 return False
             pts = 1
             for d in range(3):
                 pts *= max(1, e[d] - b[d])
             # the fold pays on large levels (one read-modify-write pass less) and on launch-bound ones (rows shorter than 64 points: one
             # kernel less); in between the separate correction is faster
-            if X.level != D.level - 1 or (pts < self.fused_prolong_min_points and D.layout.inner[0] >= 64) or \
+            if (pts < self.fused_prolong_min_points and D.layout.inner[0] >= 64) or \
                     (D.bc_fn is not None and (D.name, D.level, ds) not in self._bc_valid):
                 return False
-            self._pending = dict(kind="prolong", D=D, ds=ds, X=X, xs=xs, b=b, e=e)
-            return True
-        return False
+        else:
+            return False
+        self._pending = Pending(k, b, e)
+        return True
 
     def _flush_pending(self):
         """Run the pending loop as the statement it is."""
         P, self._pending = self._pending, None
-        if P is None:
-            return
-        ops, D = self.ops, P["D"]
-        self.launches += 1
-        if P["kind"] == "residual":
-            U, F = P["U"], P["F"]
-            ops.stencil_op(1, U.lc, U.data(P["us"]), F.lc, F.data(P["fs"]), D.lc, D.data(P["ds"]), P["A"], 0.0, -1, P["b"], P["e"])
-        elif P["kind"] == "zero":
-            ops.set(D.lc, D.data(P["ds"]), 0.0, P["b"], P["e"])
-        else:
-            X = P["X"]
-            ops.prolong_add(X.lc, X.data(P["xs"]), D.lc, D.data(P["ds"]), P["b"], P["e"])
+        if P is not None:
+            self._launch(P.stmt, P.b, P.e, None)
 
     # -- the gate: every statement passes here while a loop is pending ------------------------------------------------------
     def _gate(self, s, fr) -> bool:
@@ -122,24 +121,25 @@ class LazyFusions:
                 self._flush_pending()
             return False
         P = self._pending
+        pk = P.stmt
         if k == "comm":
             return False                      # a block without neighbours: the generated exch function is empty
         if k == "applybc":
             f, _ = self._field(s[1], fr)
-            if f is P["D"]:
+            if f is pk.D:
                 return False                  # boundary planes only: commutes with the pending loop over inner points
-        elif k == "loop" and P["kind"] == "residual":
+        elif k == "loop" and pk.kind == "residual":
             if self._consume_residual(s, fr):
                 return True
-        elif k == "color" and P["kind"] in ("zero", "prolong"):
+        elif k == "color" and pk.kind in ("set", "prolong_add"):
             from .exa4 import _parity_expr
 
             shift = _parity_expr(s[1][0], self.nd) if len(s[1]) == 1 else None
             if shift is not None:
-                kw = dict(zero_input=True) if P["kind"] == "zero" else dict(correction_from=(P["X"], P["xs"]))
+                kw = dict(zero_input=True) if pk.kind == "set" else dict(correction_from=(pk.U, pk.us))
                 self._pending = None          # the sweep either absorbs it ...
-                if self._try_fused_sweep(s[2], (0 - shift) % 2, fr, only_field=P["D"], **kw):
-                    self.fusions["zero_start" if P["kind"] == "zero" else "folded_correction"] += 1
+                if self._try_fused_sweep(s[2], (0 - shift) % 2, fr, only_field=pk.D, **kw):
+                    self.fusions["zero_start" if pk.kind == "set" else "folded_correction"] += 1
                     return True
                 self._pending = P             # ... or it runs first
         self._flush_pending()
@@ -160,25 +160,24 @@ class LazyFusions:
         if only is not None or where is not None or fr.colour is not None or fr.mcolour is not None or fr.contract is not None or len(body) != 1:
             return False
         st = body[0]
-        D, U, F, A = P["D"], P["U"], P["F"], P["A"]
+        pk = P.stmt
+        D, ds, U, us, F, fs, A = pk.D, pk.ds, pk.U, pk.us, pk.F, pk.fs, pk.A
         if reduction is None:
             # RHS@coarser = [scale *] Restriction * Residual
             if st[0] != "assign" or st[1] != "=" or st[2][0] != "fld":
                 return False
-            m = self._sten_times_field(st[3], fr)
-            if m is None or m[1] != "restriction":
+            k = self._recognise_or_none(st, fr)
+            if k is None or k.kind != "restrict":
                 return False
-            X, xs = self._field(m[4], fr)
-            C, cs = self._field(st[2], fr)
-            if X is not D or xs != P["ds"] or C.level != D.level - 1 or self._field(target, fr)[0] is not C:
+            C, cs = k.D, k.ds
+            if k.U is not D or k.us != ds or C.level != D.level - 1 or self._field(target, fr)[0] is not C:
                 return False
             if not self._dead_after((D.name, D.level)):
                 return False
             cb, ce = self.domain.loop_bounds(C.layout)
             self._pending = None
             self.launches += 1
-            self.ops.residual_restrict(U.lc, U.data(P["us"]), F.lc, F.data(P["fs"]), D.lc, D.data(P["ds"]), A, C.lc, C.data(cs), m[0],
-                                       P["b"], P["e"], cb, ce)
+            self.ops.residual_restrict(U.lc, U.data(us), F.lc, F.data(fs), D.lc, D.data(ds), A, C.lc, C.data(cs), k.s, P.b, P.e, cb, ce)
             self.fusions["residual_restrict"] += 1
             return True
         # Var s = 0; loop over Residual with reduction ( + : s ) { s += Residual * Residual }
@@ -192,7 +191,7 @@ class LazyFusions:
         X, xs = self._field(rhs[2], fr)
         Y, ys = self._field(rhs[3], fr)
         f, _ = self._field(target, fr)
-        if X is not D or Y is not D or xs != P["ds"] or ys != P["ds"] or f is not D:
+        if X is not D or Y is not D or xs != ds or ys != ds or f is not D:
             return False
         boxes, colour = self._loop_boxes(f, only, where, reduction, fr)
         if colour is not None or len(boxes) != 1 or not self._dead_after((D.name, D.level)):
@@ -200,7 +199,7 @@ class LazyFusions:
         b, e = boxes[0]
         self._pending = None
         self.launches += 1
-        t = self.ops.residual_norm2(U.lc, U.data(P["us"]), F.lc, F.data(P["fs"]), A, b, e, D.lc, D.data(P["ds"]))
+        t = self.ops.residual_norm2(U.lc, U.data(us), F.lc, F.data(fs), A, b, e, D.lc, D.data(ds))
         fr.vars[var] = fr.vars[var] + self.comm.reduce_value(t, "sum")
         self.fusions["residual_norm"] += 1
         return True

@@ -3,11 +3,14 @@
 statements they stand in -- `D = A * U + S * U`, `D = F - ( A * U + S * U )`, `D += A * U + S * U` (one examg_nl_op each) and the
 Newton smoother `D = U + w * ( ( F - ( A * U + S * U ) ) / ( diag ( A ) + <point expression over U> ) )`, out of place or in place under
 the red-black colouring (one examg_nl_smooth).  A is a constant stencil, S the coefficient-expression stencil; the field S reads need
-not be U (`gamSten@coarser * Approximation@coarser` reads Solution).  Everything else around such a stencil is refused by name."""
+not be U (`gamSten@coarser * Approximation@coarser` reads Solution).  Everything else around such a stencil is refused by name.
+The statements are RECOGNISED here (`_recognise_nonlinear`, the first form the recogniser of exa4_statements.py tries) and launched by
+that module's launcher."""
 from __future__ import annotations
 
 from .exa4_common import _Frame
 from .exa4_parser import Exa4Unsupported, _contains, _walk
+from .exa4_statements import LoopStmt
 from .lib import MAX_NL_EXPR, NL_ADD, NL_APPLY, NL_RESIDUAL, NL_STACK, NlExprC
 
 _FORMS = "A * U + S * U, F - ( A * U + S * U ), D += A * U + S * U and U + w * ( ( F - ( A * U + S * U ) ) / ( diag ( A ) + d ( U ) ) )"
@@ -39,7 +42,8 @@ class Nonlinear:
         return e
 
     def _names_coef_expr(self, e) -> bool:
-        return any(n and n[0] == "sten" and n[1] in self._stencil_decls and self._coef_expr(n[1]) is not None for n in _walk(e))
+        some = self._field_stencils()     # (exa4_systems.py) empty for most programs: nothing to walk
+        return bool(some) and any(n and n[0] == "sten" and n[1] in some and self._coef_expr(n[1]) is not None for n in _walk(e))
 
     def _nl_program(self, e, lvl: int, what: str):
         """examg_nlexpr_t of a point expression over one field access: the access compiles to EXAMG_OP_U.  Globals are folded into the
@@ -103,31 +107,22 @@ class Nonlinear:
             if X.layout.transform:
                 raise Exa4Unsupported("%s on colour-split field %s" % (what, X.name))
 
-    def _exec_nonlinear(self, op, lhs, rhs, D, ds, b, e, colour, fr):
-        """A loop statement that names a coefficient-expression stencil: one launch, or a refusal by name."""
-        ops = self.ops
+    def _recognise_nonlinear(self, op, lhs, rhs, D, ds, colour, fr):
+        """A loop statement that names a coefficient-expression stencil: the record of its one launch, or a refusal by name."""
         what = "semilinear operator"
-        m = self._nl_sum(rhs, fr)
-        if m is not None and op in ("=", "+="):
+        m, F = self._nl_sum(rhs, fr) if op in ("=", "+=") else None, None
+        if m is None and op == "=" and rhs[0] == "bin" and rhs[1] == "-" and rhs[2][0] == "fld":
+            m, F = self._nl_sum(rhs[3], fr), rhs[2]
+        if m is not None:
             A, U, us, Q, qs, c = self._nl_operands(m, fr, what)
-            self._nl_plain(what, D, U, Q)
+            FF, fs = self._field(F, fr) if F is not None else (None, 0)
+            self._nl_plain(what, D, U, Q, *(() if FF is None else (FF,)))
             if colour is not None:
                 raise Exa4Unsupported("%s in a coloured loop outside the smoother" % what)
             if D is U and ds == us:
                 raise Exa4Unsupported("%s assigned to the field it acts on" % what)
-            mode = NL_APPLY if op == "=" else NL_ADD
-            return ops.nl_op(mode, U.lc, U.data(us), Q.lc, Q.data(qs), None, None, D.lc, D.data(ds), A, c, b, e)
-        if op == "=" and rhs[0] == "bin" and rhs[1] == "-" and rhs[2][0] == "fld":
-            m = self._nl_sum(rhs[3], fr)
-            if m is not None:
-                A, U, us, Q, qs, c = self._nl_operands(m, fr, what)
-                F, fs = self._field(rhs[2], fr)
-                self._nl_plain(what, D, U, Q, F)
-                if colour is not None:
-                    raise Exa4Unsupported("%s in a coloured loop outside the smoother" % what)
-                if D is U and ds == us:
-                    raise Exa4Unsupported("%s assigned to the field it acts on" % what)
-                return ops.nl_op(NL_RESIDUAL, U.lc, U.data(us), Q.lc, Q.data(qs), F.lc, F.data(fs), D.lc, D.data(ds), A, c, b, e)
+            mode = NL_RESIDUAL if F is not None else (NL_APPLY if op == "=" else NL_ADD)
+            return LoopStmt("nl_op", D, ds, U, us, FF, fs, A, prog=(mode, Q, qs, c))
         # D = U + w * ( ( F - ( A * U + S * U ) ) / ( diag ( A ) + d ) )   |   U += w * ( .. )
         src = t = None
         if op == "=" and rhs[0] == "bin" and rhs[1] == "+" and rhs[2][0] == "fld":
@@ -161,7 +156,6 @@ class Nonlinear:
                     raise Exa4Unsupported("coloured %s into another slot" % what)
                 if colour is not None and not A.faces_only:
                     raise Exa4Unsupported("in-place %s: the red-black colouring does not decouple stencil %s" % (what, m[0]))
-                return ops.nl_smooth(U.lc, U.data(us), D.lc, D.data(ds), F.lc, F.data(fs), A, c, d, float(self._eval(t[2], fr)),
-                                     -1 if colour is None else colour, b, e)
+                return LoopStmt("nl_smooth", D, ds, U, us, F, fs, A, float(self._eval(t[2], fr)), prog=(c, d))
         names = sorted({n[1] for n in _walk(rhs) if n and n[0] == "sten" and n[1] in self._stencil_decls and self._coef_expr(n[1]) is not None})
         raise Exa4Unsupported("coefficient-expression stencil %s outside the forms %s" % (", ".join(names), _FORMS))

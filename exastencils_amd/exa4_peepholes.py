@@ -1,22 +1,12 @@
 """Peepholes of the ExaSlang-4 interpreter (mixin of exa4.Exa4Program): statement groups that run as ONE pass over HBM with the same
 bits -- the red-black sweep of a `color with` block (examg_rbgs_sweep_fused), pairs of slotted Jacobi steps and contracting loops
 (examg_jacobi2_boxes), and a coarsest-level function that is statement for statement the generated CG solver (examg_cg_coarse*).
-The cross-STATEMENT forms (pending loops + liveness) are in exa4_fusion.py."""
+The cross-STATEMENT forms (pending loops + liveness) are in exa4_fusion.py.  What a loop statement is, the peepholes ask the one
+recogniser of exa4_statements.py (`_match_smoother`); only the coarse-CG matcher, which reads a whole function body, uses the pattern
+helpers `_residual_form` and `_sten_times_field` itself."""
 from __future__ import annotations
 
-import math
-import os
-import random
-import re
-import time
-from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
-
-from . import knowledge as _knowledge
-from .comm import Communicator
-from .domain import RectDomain
 from .field import Field, Stencil
-from .layout import FieldLayout
 from .exa4_parser import (Exa4SyntaxError, Exa4Unsupported, FunctionDecl, Parser, _COORD, _GRIDW, _MATH, _arith,  # noqa: F401
                           _colour_cond, _conjuncts, _const_value, _contains, _find_calls, _has_coord, _lower_cond, _parity_expr, _walk)
 from .exa4_common import (APPLY, RESIDUAL, SMOOTH, _FN_2D_ONLY, _FN_ANY_DIM, _FN_WITH_PARAM, _N_FN, _Frame, _Return, fn_eval)  # noqa: F401
@@ -25,26 +15,18 @@ from .exa4_common import (APPLY, RESIDUAL, SMOOTH, _FN_2D_ONLY, _FN_ANY_DIM, _FN
 class Peepholes:
     # -- peepholes: same results bit for bit, fewer passes over HBM ---------------------------------------------------------
     def _match_smoother(self, st, fr: _Frame):
-        """(D, dslot, U, uslot, F, fslot, A, w) if `st` is a damped-residual update  D = U + w * (F - A * U)."""
+        """(D, dslot, U, uslot, F, fslot, A, w) if the recogniser (exa4_statements.py) says `st` is a damped-residual update
+        D = U + w * (F - A * U) on plain node fields; None for every other statement, refused ones included."""
         if st[0] != "assign" or st[2][0] != "fld":
             return None
-        op, lhs, rhs = st[1], st[2], st[3]
-        src = wexpr = r = None
-        if op == "+=" and rhs[0] == "bin" and rhs[1] == "*":
-            src, wexpr, r = lhs, rhs[2], self._residual_form(rhs[3], fr)
-        elif op == "=" and rhs[0] == "bin" and rhs[1] == "+" and rhs[2][0] == "fld" and rhs[3][0] == "bin" and rhs[3][1] == "*":
-            src, wexpr, r = rhs[2], rhs[3][2], self._residual_form(rhs[3][3], fr)
-        if r is None or not self._same_access(src, r[2], fr):
+        k = self._recognise_or_none(st, fr)
+        if k is None or k.kind != "smooth":
             return None
-        D, ds = self._field(lhs, fr)
-        U, us = self._field(src, fr)
-        F, fs = self._field(r[0], fr)
-        if D.layout.is_cell or U.layout.is_cell or F.layout.is_cell:
+        if k.D.layout.is_cell or k.U.layout.is_cell or k.F.layout.is_cell:
             return None         # cell fields: ghost values depend on the interior after every step -- statement by statement
-        wv, A = self._smoother_weight(wexpr, r[1], fr)
-        if D.layout.transform or U.layout.transform or F.layout.transform:
+        if k.D.layout.transform or k.U.layout.transform or k.F.layout.transform:
             return None         # fields under a layout transformation: the plain loops (the kernel layer's one-pass forms take plain layouts)
-        return D, ds, U, us, F, fs, A, wv
+        return k.D, k.ds, k.U, k.us, k.F, k.fs, k.A, k.s
 
     @staticmethod
     def _canonical7(A: Stencil, nd: int) -> bool:

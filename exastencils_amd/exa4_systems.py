@@ -1,11 +1,13 @@
 """Coupled systems of scalar cell fields in the ExaSlang-4 interpreter (mixin of Exa4Program): point-wise coefficient stencils
 (`Stencil uvSten { [0, 0] => IxIy }`), system rows `sum_d (P_cd * F_d) + [s *] (L * F_c)`, `solve locally` inside a coloured loop
 and the point-wise set-up statements of Benchmark/OptFlow2D/2D_FD_OptFlow.exa4.  One launch per loop: examg_sys_op with a one-row
-mask, examg_sys_relax, examg_pointwise_mul (include/examg.h).  Cell fields are never deferred or fused (exa4_fusion.py), so these
-loops run where they stand."""
+mask, examg_sys_relax, examg_pointwise_mul (include/examg.h).  System rows and point-wise statements are RECOGNISED here, for the one
+recogniser of loop-body assignments, and launched by its launcher (exa4_statements.py); `solve locally` is a whole-loop form and issues
+its own call.  Cell fields are never deferred or fused (exa4_fusion.py), so these loops run where they stand."""
 from __future__ import annotations
 
 from .exa4_parser import Exa4Unsupported, _contains
+from .exa4_statements import LoopStmt
 from .field import Stencil
 from .lib import SYS_APPLY, SYS_RESIDUAL
 
@@ -21,9 +23,9 @@ class Systems:
     def _coef_field(self, name: str):
         """The field expression of a point-wise coefficient stencil (its single centre entry is a field access), None for any
         other stencil.  A field anywhere else in a stencil is refused by name."""
-        sd = self._stencil_decls.get(name)
-        if sd is None or not any(_contains(e, ("fld",)) for _, e in sd.entries):
+        if name not in self._field_stencils():
             return None
+        sd = self._stencil_decls[name]
         if not any(e[0] == "fld" for _, e in sd.entries):
             return None       # expressions over fields only: exa4_nonlinear.py names what it refuses
         if len(sd.entries) != 1:
@@ -34,6 +36,13 @@ class Systems:
         if e[0] != "fld":
             return None       # an expression over a field: a coefficient-expression stencil (exa4_nonlinear.py)
         return e
+
+    def _field_stencils(self):
+        """The declared stencils with a field access in an entry -- these and the coefficient-expression stencils of exa4_nonlinear.py
+        are among them, most programs have none.  Every loop statement is asked whether it names one: found once, declarations stay."""
+        if "field stencils" not in self._fn_cache:
+            self._fn_cache["field stencils"] = {n for n, sd in self._stencil_decls.items() if any(_contains(e, ("fld",)) for _, e in sd.entries)}
+        return self._fn_cache["field stencils"]
 
     # -- system rows ----------------------------------------------------------------------------------------------------------
     def _system_row(self, e, fr):
@@ -91,16 +100,17 @@ class Systems:
             if F.layout != fields[0][0].layout:
                 raise Exa4Unsupported("%s: %s and %s have different layouts" % (what, fields[0][0].name, F.name))
 
-    def _exec_system_assign(self, D, ds, rhs, b, e, colour, fr) -> bool:
-        """`X = row` (EXAMG_SYS_APPLY) and `X = rhs - ( row )` (EXAMG_SYS_RESIDUAL): one examg_sys_op with a one-row mask."""
+    def _recognise_system_row(self, D, ds, rhs, colour, fr):
+        """`X = row` (EXAMG_SYS_APPLY) and `X = rhs - ( row )` (EXAMG_SYS_RESIDUAL): the record of one examg_sys_op with a one-row mask,
+        None when the expression is no system row."""
         mode, F, row = SYS_APPLY, None, rhs
         if rhs[0] == "bin" and rhs[1] == "-" and rhs[2][0] == "fld":
             mode, F, row = SYS_RESIDUAL, rhs[2], rhs[3]
-        if not _contains(row, ("sten",)):
-            return False
+        if not self._field_stencils() or not _contains(row, ("sten",)):      # (no row without a coefficient term)
+            return None
         r = self._system_row(row, fr)
         if r is None:
-            return False
+            return None
         terms, L, own = r
         if colour is not None:
             raise Exa4Unsupported("system row in a coloured loop outside solve locally")
@@ -120,15 +130,9 @@ class Systems:
             d = [k for k, (Y, t) in enumerate(us) if Y is X and t == s][0]
             if g[c][d] is not None:
                 raise Exa4Unsupported("system row with two coefficient terms on %s" % X.name)
-            g[c][d] = G.data(gs)
-        f, dst = [None] * n, [None] * n
-        lf = us[0][0].lc
-        if F is not None:
-            FF, fs = self._field(F, fr)
-            f[c], lf = FF.data(fs), FF.lc
-        dst[c] = D.data(ds)
-        self.ops.sys_op(mode, us[0][0].lc, [X.data(s) for X, s in us], lf, f, terms[0][0].lc, g, D.lc, dst, L, 1 << c, b, e)
-        return True
+            g[c][d] = (G, gs)
+        FF, fs = self._field(F, fr) if F is not None else (None, 0)
+        return LoopStmt("sys_row", D, ds, F=FF, fs=fs, A=L, prog=(mode, us, terms[0][0], g, c))
 
     # -- solve locally --------------------------------------------------------------------------------------------------------
     def _exec_solve_locally(self, st, boxes, colour, fr):
@@ -183,25 +187,16 @@ class Systems:
             self.ops.sys_relax(us[0][0].lc, [X.data(s) for X, s in us], f[0][0].lc, [X.data(s) for X, s in f], coefs[0][0].lc, g, L, w, colour, b, e)
 
     # -- point-wise set-up statements ---------------------------------------------------------------------------------------------
-    def _exec_pointwise(self, D, ds, rhs, b, e, fr) -> bool:
-        """`X = Y * Z`, `X = -Y * Z` (examg_pointwise_mul) and `X = Y - Z` (a copy and examg_axpby: x + (-1.0 * y) is bitwise x - y)."""
-        ops = self.ops
+    def _recognise_pointwise(self, D, ds, rhs, fr):
+        """`X = Y * Z`, `X = -Y * Z` (examg_pointwise_mul) and `X = Y - Z` (a copy and examg_axpby), None for anything else."""
         if not D.layout.is_cell:      # the set-up loops of the cell-field systems; node fields keep their refusal
-            return False
+            return None
         if rhs[0] == "bin" and rhs[1] == "*" and rhs[3][0] == "fld" and (rhs[2][0] == "fld" or (rhs[2][0] == "neg" and rhs[2][1][0] == "fld")):
             s, y = (1.0, rhs[2]) if rhs[2][0] == "fld" else (-1.0, rhs[2][1])
-            Y, ys = self._field(y, fr)
-            Z, zs = self._field(rhs[3], fr)
-            ops.pointwise_mul(Y.lc, Y.data(ys), Z.lc, Z.data(zs), D.lc, D.data(ds), s, b, e)
-            return True
+            return LoopStmt("pointwise_mul", D, ds, *self._field(y, fr), *self._field(rhs[3], fr), s=s)
         if rhs[0] == "bin" and rhs[1] == "-" and rhs[2][0] == "fld" and rhs[3][0] == "fld":
-            Y, ys = self._field(rhs[2], fr)
             Z, zs = self._field(rhs[3], fr)
             if Z is D and zs == ds:
                 raise Exa4Unsupported("X = Y - X")
-            if not (Y is D and ys == ds):
-                ops.axpby(Y.lc, Y.data(ys), D.lc, D.data(ds), 1.0, 0.0, b, e)
-                self.launches += 1
-            ops.axpby(Z.lc, Z.data(zs), D.lc, D.data(ds), -1.0, 1.0, b, e)
-            return True
-        return False
+            return LoopStmt("pointwise_sub", D, ds, *self._field(rhs[2], fr), Z, zs)
+        return None

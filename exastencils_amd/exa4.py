@@ -104,6 +104,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             lo = tuple(float(_const_value(e)) for e in self.ast.domain[1]) + (0.0,) * (3 - self.nd)
             hi = tuple(float(_const_value(e)) for e in self.ast.domain[2]) + (1.0,) * (3 - self.nd)
         self._merged_blocks = None
+        self._fragments = d["frags_total"][0] * d["frags_total"][1] * d["frags_total"][2]      # of the knowledge file: what a per-fragment loop order depends on
         if domain is None:
             # one process: the reference's blocks x fragments become one fragment of the same global grid
             flen = tuple(d["frags_total"][i] * d["frag_len"][i] for i in range(3))
@@ -1219,7 +1220,10 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                 self._bc_epoch[(tf.name, tf.level)] = self._bc_epoch.get((tf.name, tf.level), 0) + 1
                 self._bc_valid -= {(tf.name, tf.level, sl) for sl in range(tf.num_slots)}
             for b, e in boxes:
-                self._launch(self._recognise_assign(st, fr, colour), b, e, colour)
+                k = self._recognise_assign(st, fr, colour)
+                if self._is_lexicographic(k, colour):
+                    self._check_lexicographic(k, only, where, fr)
+                self._launch(k, b, e, colour)
 
     def _exec_reduction(self, f: Field, boxes, reduction, body, fr: _Frame):
         op, var = reduction

@@ -183,6 +183,35 @@ class Statements:
                 Exa4Unsupported("prolongation between levels %d and %d" % (X.level, D.level))
         return LoopStmt(("restrict" if up > 0 else "prolong_add") + ("_cell" if cell else ""), D, ds, X, xs, s=m[0])
 
+    # -- the loop without a colouring ---------------------------------------------------------------------------------------
+    def _is_lexicographic(self, k: LoopStmt, colour) -> bool:
+        """An in-place smoother update with no colour on a kernel layer that has the lexicographic sweep (a layer without it keeps
+        the launcher's refusal)."""
+        return k.kind == "smooth" and colour is None and k.D is k.U and k.ds == k.us and hasattr(self.ops, "gs_sweep")
+
+    def _check_lexicographic(self, k: LoopStmt, only, where, fr: _Frame):
+        """What the lexicographic sweep cannot be, by name.  Its result depends on the order of the points of ONE fragment: the reference
+        sweeps every fragment on its own, so merged fragments, several blocks or a periodic axis would compute another iteration."""
+        what = "lexicographic Gauss-Seidel (in-place smoother update without colouring)"
+        if only is not None or where is not None:
+            raise Exa4Unsupported("%s in a loop with `only` or `where`" % what)
+        if fr.contract is not None:
+            raise Exa4Unsupported("%s under contraction" % what)
+        if self._fragments != 1:
+            raise Exa4Unsupported("%s: the knowledge file describes %d fragments, and every fragment sweeps on its own -- one merged "
+                                  "block would compute another iteration" % (what, self._fragments))
+        if self.domain.world_size != 1:
+            raise Exa4Unsupported("%s on %d blocks (world_size must be 1)" % (what, self.domain.world_size))
+        if any(self.domain.periodic):
+            raise Exa4Unsupported("%s on a periodic domain" % what)
+        for X in (k.D, k.F):
+            if X.layout.is_cell:
+                raise Exa4Unsupported("%s over cell field %s" % (what, X.name))
+            if X.layout.transform:
+                raise Exa4Unsupported("%s over colour-split field %s" % (what, X.name))
+        if k.A.cfield is not None and k.A.ctransform:
+            raise Exa4Unsupported("%s with an entry-fastest coefficient field" % what)
+
     # -- the launcher ---------------------------------------------------------------------------------------------------
     def _launch(self, k: LoopStmt, b, e, colour):
         """Issue the loop `k` stands for on the box [b, e): the only kernel-layer calls of loop-body assignments, and their count."""
@@ -194,7 +223,11 @@ class Statements:
         if kind == "smooth":
             in_place = D is U and k.ds == k.us
             if in_place and colour is None:
-                raise Exa4Unsupported("in-place smoother update without colouring (lexicographic Gauss-Seidel)")
+                if not hasattr(ops, "gs_sweep"):
+                    raise Exa4Unsupported("in-place smoother update without colouring (lexicographic Gauss-Seidel)")
+                self.launches += 1
+                ops.gs_sweep(U.lc, u, lf, f, k.A, k.s, b, e)       # the sequential nest's values (examg_gs_sweep); checked by _check_lexicographic
+                return
             if not in_place and colour is not None:
                 raise Exa4Unsupported("coloured update into another slot")
         self.launches += 1

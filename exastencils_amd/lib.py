@@ -128,6 +128,7 @@ SYMBOLS = [
     "examg_stencil_op_coloured", "examg_mcgs_sweep", "examg_mcgs_one_pass_eligible",
     "examg_sys_op", "examg_sys_relax", "examg_pointwise_mul",
     "examg_nl_op", "examg_nl_smooth",
+    "examg_gs_sweep", "examg_gs_route",
 ]
 
 COMM_ID_BYTES = 128
@@ -136,6 +137,7 @@ EXCH_DUP, EXCH_GHOST, EXCH_ALL, EXCH_CONCURRENT_AXES = 1, 2, 3, 4
 PASS_TMP_PLANES_VALID = 8
 BC_DIRICHLET, BC_NEUMANN = 0, 1
 CG_ALPHA_FROM_NORM, CG_NO_BC, CG_ZERO_START = 1, 2, 4
+GS_REFUSED, GS_EMPTY, GS_ONE_WORKGROUP, GS_TILED, GS_PER_HYPERPLANE = -1, 0, 1, 2, 3      # examg_gs_route
 
 
 class CrandStateC(C.Structure):
@@ -257,6 +259,8 @@ def load(path=None):
     np_ = C.POINTER(NlExprC)
     L.examg_nl_op.argtypes = [C.c_int, lp, vp, lp, vp, lp, vp, lp, vp, sp, np_, ip, ip, vp]
     L.examg_nl_smooth.argtypes = [lp, vp, lp, vp, lp, vp, sp, np_, np_, C.c_double, C.c_int, ip, ip, vp]
+    L.examg_gs_sweep.argtypes = [lp, vp, lp, vp, sp, C.c_double, ip, ip, vp]
+    L.examg_gs_route.argtypes = [lp, lp, sp, ip, ip]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("examg_version", "examg_last_error", "examg_device_count", "examg_reduce_work_bytes", "examg_exchange_workspace_bytes",
@@ -282,6 +286,13 @@ def load(path=None):
         L.examg_debug_cg.restype = C.c_int
         L.examg_debug_cg_route.argtypes = [lp, lp, lp, lp, lp, sp, C.c_uint32, ip, ip, C.c_uint32]
         L.examg_debug_cg_route.restype = C.c_int
+    if hasattr(L, "examg_debug_gs_route"):           # debug build only: the route of examg_gs_sweep forced, its schedule point by point
+        L.examg_debug_gs_route.argtypes = [C.c_int]
+        L.examg_debug_gs_route.restype = C.c_int
+        L.examg_debug_gs_launches.argtypes = [lp, lp, sp, ip, ip]
+        L.examg_debug_gs_launches.restype = C.c_int
+        L.examg_debug_gs_schedule.argtypes = [lp, lp, sp, ip, ip, vp, vp]
+        L.examg_debug_gs_schedule.restype = C.c_int
     _libs[path] = L
     if path == LIB_PATH:
         _lib = L

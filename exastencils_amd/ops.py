@@ -105,6 +105,17 @@ class HipOps:
         sc, cc = st.c_struct(self.ptr), col.c_struct()
         return bool(self.L.examg_mcgs_one_pass_eligible(C.byref(lu), C.byref(lf), C.byref(sc), C.byref(cc), ivec(begin), ivec(end)))
 
+    def gs_sweep(self, lu, u, lf, rhs, st: Stencil, w: float, begin, end):
+        """One lexicographic Gauss-Seidel sweep in place on u: the sequential nest of the loop, x fastest, bit for bit (examg_gs_sweep)."""
+        sc = st.c_struct(self.ptr)
+        check(self.L.examg_gs_sweep(C.byref(lu), self.ptr(u), C.byref(lf), self.ptr(rhs), C.byref(sc), float(w), ivec(begin), ivec(end),
+                                    self._stream()), "examg_gs_sweep")
+
+    def gs_route(self, lu, lf, st: Stencil, begin, end) -> int:
+        """What gs_sweep does with these arguments: lib.GS_REFUSED (the reason in examg_last_error), GS_EMPTY, GS_ONE_WORKGROUP, GS_TILED, GS_PER_HYPERPLANE."""
+        sc = st.c_struct(self.ptr)
+        return int(self.L.examg_gs_route(C.byref(lu), C.byref(lf), C.byref(sc), ivec(begin), ivec(end)))
+
     def rbgs_sweep_fused(self, lu, u_in, u_out, lf, rhs, st: Stencil, w: float, first: int, begin, end):
         sc = st.c_struct(self.ptr)
         check(self.L.examg_rbgs_sweep_fused(C.byref(lu), self.ptr(u_in), self.ptr(u_out), C.byref(lf), self.ptr(rhs),

@@ -700,6 +700,7 @@ class ConfigL3:
     frag_len: Tuple[int, int, int] = (1, 1, 1)
     # 'jacobi' (2 slots) | 'rbgs' | 'mcgs': the 2^nd-colour Gauss-Seidel sweep `color with { i0 % 2, i1 % 2 [, i2 % 2], communicate
     # Solution, loop over Solution { .. in place .. } }` -- what red-black is for star stencils, for stencils with diagonal neighbours
+    # | 'gs': the lexicographic sweep, the in-place loop without `color with` (examg_gs_sweep; one block only)
     smoother: str = "jacobi"
     omega: float = 0.8
     n_smooth: int = 3
@@ -742,13 +743,20 @@ class SolverFromL3(_Program):
         self.cfg = cfg
         nd, dom, ops = cfg.nd, self.domain, self.ops
         lo, hi = cfg.min_level, cfg.max_level
-        if cfg.smoother not in ("jacobi", "rbgs", "mcgs"):
+        if cfg.smoother not in ("jacobi", "rbgs", "mcgs", "gs"):
             raise ValueError("ConfigL3.smoother %r" % (cfg.smoother,))
-        if cfg.smoother == "mcgs":
+        if cfg.smoother in ("mcgs", "gs"):
             # the one-pass forms of the other two smoothers have no multi-colour counterpart: asking for one is a mistake, not a no-op
             fused = [n for n in ("temporal_blocking", "fused_rbgs", "fused_prolong_min_points", "fused_zero_start", "fused_smooth_residual")
                      if getattr(cfg, n)]
-            assert not fused, "ConfigL3(smoother='mcgs') with %s: these options belong to the Jacobi / red-black smoothers" % ", ".join(fused)
+            assert not fused, "ConfigL3(smoother=%r) with %s: these options belong to the Jacobi / red-black smoothers" % (cfg.smoother, ", ".join(fused))
+        if cfg.smoother == "gs":
+            # the reference sweeps every fragment on its own: the result depends on the decomposition, and only one block is one fragment
+            if dom.world_size != 1:
+                raise ValueError("ConfigL3(smoother='gs'): a lexicographic sweep is per fragment; %d blocks would compute another iteration "
+                                 "(world_size must be 1)" % dom.world_size)
+            if any(dom.periodic):
+                raise ValueError("ConfigL3(smoother='gs'): a periodic axis makes the block its own neighbour; the lexicographic sweep has no form for it")
         nslots = 2 if cfg.smoother == "jacobi" else 1
         prm = (cfg.kappa,)
         self.Solution: Dict[int, Field] = {}
@@ -881,6 +889,11 @@ class SolverFromL3(_Program):
                 for c in col.colours():
                     self.communicate(S, S.active)
                     self.ops.stencil_op_coloured(SMOOTH, S.lc, S.data(), F.lc, F.data(), S.lc, S.data(), A, self._w(l), c, b, e)
+        elif self.cfg.smoother == "gs":
+            # communicate Solution, loop over Solution { Solution += w * (RHS - A * Solution) }: no colouring, the nest's order
+            assert correction_from is None and not zero_input
+            self.communicate(S, S.active)
+            self.ops.gs_sweep(S.lc, S.data(), F.lc, F.data(), A, self._w(l), b, e)
         else:                                   # Testing/Smoothers/RBGS.exa4:125-133
             assert correction_from is None and not zero_input
             for colour in (0, 1):

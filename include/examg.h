@@ -179,6 +179,30 @@ int examg_mcgs_sweep(const examg_layout_t *lu, double *u, const examg_layout_t *
 int examg_mcgs_one_pass_eligible(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const examg_colouring_t *col,
                                  const int32_t *begin, const int32_t *end);
 
+/* ---- lexicographic Gauss-Seidel: the in-place `loop over u { u = u + ww * (rhs - A * u) }` with NO colouring, the one loop whose result
+ * depends on the order of its points.  The reference prints it as a sequential nest, x fastest; examg_gs_sweep computes exactly
+ *     for i2 in [b2, e2): for i1 in [b1, e1): for i0 in [b0, e0):
+ *         u[i] = u[i] + ww * (rhs[i] - fold_k(c_k * u[i + o_k]))
+ * in place.  Arithmetic order: acc = c_0 * u[i + o_0]; acc = acc + c_k * u[i + o_k] for k = 1 .. nent - 1 in entry order; then
+ * rhs[i] - acc; then ww * (..); then u[i] + (..) -- no contraction.  ww as in examg_stencil_op(EXAMG_SMOOTH): the folded constant `w`
+ * for constant stencils; per point (1.0 / c_diag) * w or w / c_diag for stencil fields, as st->wform names.  A point reads the NEW value
+ * of every neighbour that precedes it in the nest and lies inside the box, and the OLD value of every other one: later points, and
+ * everything outside the box (boundary planes, ghost layers).  Nothing outside the box is written.  Forward sweep only (the reference
+ * generates no backward one).  The kernels update the points on a parallel schedule that respects every dependency of the nest; as
+ * each point is computed with the same operations in the same order, the result is the nest's bit for bit.
+ * Supported: 2-D and 3-D node fields, u and rhs each in its own layout; every stencil whose offsets lie in {-1, 0, 1}^d -- 5-, 9-, 7-,
+ * 27-point, asymmetric ones, entries in any order -- constant or a stencil field in planes, both weight forms.  Refused (non-zero,
+ * examg_last_error, nothing written): offsets of reach 2, entry-fastest coefficient records, colour-split layouts, cell layouts (no
+ * duplicate layers), a box whose one-point shell leaves the u allocation.  An empty box is a no-op that returns 0.
+ * A sweep is a sequence of launches of one kernel on `stream` (or a single launch for small boxes): no host synchronisation, no
+ * allocation -- capturable into a hipGraph; no workgroup ever waits for another one. */
+int examg_gs_sweep(const examg_layout_t *lu, double *u, const examg_layout_t *lf, const double *rhs, const examg_stencil_t *st, double w,
+                   const int32_t *begin, const int32_t *end, examg_stream_t stream);
+/* What examg_gs_sweep does with these arguments, decided from them alone (nothing is launched): -1 refused (error text set), 0 empty
+ * box, 1 one workgroup walks the point hyperplanes of the whole box, 2 tiles, one launch per tile hyperplane, 3 one launch per point
+ * hyperplane (stencil fields of more than 9 entries on boxes of more than 128^3 points, where it is the faster schedule). */
+int examg_gs_route(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const int32_t *begin, const int32_t *end);
+
 /* One full red-black sweep (colour `first`, then the other) out of place, in ONE pass over HBM: the points of
  * [begin,end) of u_out receive exactly (bit for bit) what the two examg_rbgs_colour calls would leave there;
  * outside the box at most the one-stencil-reach shell is touched, and only by copying u_in's values there; the

@@ -341,42 +341,75 @@ __host__ __device__ __forceinline__ void point_position(const Geom &g, int i0, i
   }
 }
 
-// A point function: a postfix program (include/examg.h), evaluated in the order of the expression tree.
+// A point function: a postfix program (include/examg.h), evaluated in the order of the expression tree.  W: the program may read the
+// widths of the point's cell (EXAMG_OP_WX/WY/WZ: the _grid entry points); without W they are unknown opcodes like any other.
+template <bool W>
+__device__ __forceinline__ double expr_eval(const examg_expr_t &e, double x, double y, double z, double wx, double wy, double wz) {
+  double st[24];
+  int sp = 0;
+  for (int i = 0; i < e.n; ++i) {
+    switch (e.op[i]) {
+      case EXAMG_OP_CONST: st[sp++] = e.c[i]; break;
+      case EXAMG_OP_X: st[sp++] = x; break;
+      case EXAMG_OP_Y: st[sp++] = y; break;
+      case EXAMG_OP_Z: st[sp++] = z; break;
+      case EXAMG_OP_ADD: --sp; st[sp - 1] = st[sp - 1] + st[sp]; break;
+      case EXAMG_OP_SUB: --sp; st[sp - 1] = st[sp - 1] - st[sp]; break;
+      case EXAMG_OP_MUL: --sp; st[sp - 1] = st[sp - 1] * st[sp]; break;
+      case EXAMG_OP_DIV: --sp; st[sp - 1] = st[sp - 1] / st[sp]; break;
+      case EXAMG_OP_NEG: st[sp - 1] = -st[sp - 1]; break;
+      case EXAMG_OP_SIN: st[sp - 1] = sin(st[sp - 1]); break;
+      case EXAMG_OP_COS: st[sp - 1] = cos(st[sp - 1]); break;
+      case EXAMG_OP_EXP: st[sp - 1] = exp(st[sp - 1]); break;
+      case EXAMG_OP_SINH: st[sp - 1] = sinh(st[sp - 1]); break;
+      case EXAMG_OP_COSH: st[sp - 1] = cosh(st[sp - 1]); break;
+      case EXAMG_OP_SQRT: st[sp - 1] = sqrt(st[sp - 1]); break;
+      case EXAMG_OP_POW: --sp; st[sp - 1] = pow(st[sp - 1], st[sp]); break;
+      case EXAMG_OP_TAN: st[sp - 1] = tan(st[sp - 1]); break;
+      case EXAMG_OP_LOG: st[sp - 1] = log(st[sp - 1]); break;
+      case EXAMG_OP_FABS: st[sp - 1] = fabs(st[sp - 1]); break;
+      case EXAMG_OP_MAX: --sp; st[sp - 1] = fmax(st[sp - 1], st[sp]); break;
+      case EXAMG_OP_MIN: --sp; st[sp - 1] = fmin(st[sp - 1], st[sp]); break;
+      case EXAMG_OP_TANH: st[sp - 1] = tanh(st[sp - 1]); break;
+      default:
+        if (W && e.op[i] >= EXAMG_OP_WX && e.op[i] <= EXAMG_OP_WZ) st[sp++] = e.op[i] == EXAMG_OP_WX ? wx : (e.op[i] == EXAMG_OP_WY ? wy : wz);
+        else st[sp++] = __builtin_nan("");
+        break;
+    }
+  }
+  return st[0];
+}
 struct ExprEval {
   examg_expr_t e;
-  __device__ double operator()(double x, double y, double z) const {
-    double st[24];
-    int sp = 0;
-    for (int i = 0; i < e.n; ++i) {
-      switch (e.op[i]) {
-        case EXAMG_OP_CONST: st[sp++] = e.c[i]; break;
-        case EXAMG_OP_X: st[sp++] = x; break;
-        case EXAMG_OP_Y: st[sp++] = y; break;
-        case EXAMG_OP_Z: st[sp++] = z; break;
-        case EXAMG_OP_ADD: --sp; st[sp - 1] = st[sp - 1] + st[sp]; break;
-        case EXAMG_OP_SUB: --sp; st[sp - 1] = st[sp - 1] - st[sp]; break;
-        case EXAMG_OP_MUL: --sp; st[sp - 1] = st[sp - 1] * st[sp]; break;
-        case EXAMG_OP_DIV: --sp; st[sp - 1] = st[sp - 1] / st[sp]; break;
-        case EXAMG_OP_NEG: st[sp - 1] = -st[sp - 1]; break;
-        case EXAMG_OP_SIN: st[sp - 1] = sin(st[sp - 1]); break;
-        case EXAMG_OP_COS: st[sp - 1] = cos(st[sp - 1]); break;
-        case EXAMG_OP_EXP: st[sp - 1] = exp(st[sp - 1]); break;
-        case EXAMG_OP_SINH: st[sp - 1] = sinh(st[sp - 1]); break;
-        case EXAMG_OP_COSH: st[sp - 1] = cosh(st[sp - 1]); break;
-        case EXAMG_OP_SQRT: st[sp - 1] = sqrt(st[sp - 1]); break;
-        case EXAMG_OP_POW: --sp; st[sp - 1] = pow(st[sp - 1], st[sp]); break;
-        case EXAMG_OP_TAN: st[sp - 1] = tan(st[sp - 1]); break;
-        case EXAMG_OP_LOG: st[sp - 1] = log(st[sp - 1]); break;
-        case EXAMG_OP_FABS: st[sp - 1] = fabs(st[sp - 1]); break;
-        case EXAMG_OP_MAX: --sp; st[sp - 1] = fmax(st[sp - 1], st[sp]); break;
-        case EXAMG_OP_MIN: --sp; st[sp - 1] = fmin(st[sp - 1], st[sp]); break;
-        case EXAMG_OP_TANH: st[sp - 1] = tanh(st[sp - 1]); break;
-        default: st[sp++] = __builtin_nan(""); break;
-      }
-    }
-    return st[0];
-  }
+  __device__ double operator()(double x, double y, double z) const { return expr_eval<false>(e, x, y, z, 0.0, 0.0, 0.0); }
 };
+// ... over the node tables of an axis-aligned grid (examg_grid_t): positions and the widths of the point's cell
+struct ExprEvalGrid {
+  examg_expr_t e;
+  __device__ double operator()(double x, double y, double z, double wx, double wy, double wz) const { return expr_eval<true>(e, x, y, z, wx, wy, wz); }
+};
+struct GridGeom {
+  const double *n0, *n1, *n2;   // node tables; element j is node j - ghost; null for an axis the layout does not have
+  int ghost;
+};
+static inline GridGeom make_geom(const examg_grid_t *g) { return GridGeom{g->nodes[0], g->nodes[1], g->nodes[2], g->ghost}; }
+
+// The value of a point function at iterator index (i0, i1, i2): the ONE place where the point-expression kernels (kernels_blas.hip)
+// turn an index into a position -- the uniform formula, or the tables (position x[i], width x[i + 1] - x[i]; 0.0 on an axis without table)
+template <bool CELL, class F>
+__device__ __forceinline__ double eval_point(const Geom &g, const F &fn, int i0, int i1, int i2) {
+  double px, py, pz;
+  point_position<CELL>(g, i0, i1, i2, px, py, pz);
+  return fn(px, py, pz);
+}
+template <bool CELL, class F>
+__device__ __forceinline__ double eval_point(const GridGeom &g, const F &fn, int i0, int i1, int i2) {
+  double p[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+  if (g.n0) { p[0] = g.n0[i0 + g.ghost]; w[0] = g.n0[i0 + g.ghost + 1] - p[0]; }
+  if (g.n1) { p[1] = g.n1[i1 + g.ghost]; w[1] = g.n1[i1 + g.ghost + 1] - p[1]; }
+  if (g.n2) { p[2] = g.n2[i2 + g.ghost]; w[2] = g.n2[i2 + g.ghost + 1] - p[2]; }
+  return fn(p[0], p[1], p[2], w[0], w[1], w[2]);
+}
 
 // host check of an expression program's stack discipline (kernels_blas.hip); sets the error text when it fails
 bool expr_ok(const examg_expr_t *e);

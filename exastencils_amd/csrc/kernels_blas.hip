@@ -173,17 +173,15 @@ k_dot_rows(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const doubl
 }
 
 
-template <class F, bool CELL = false>
+template <class F, bool CELL = false, class G = Geom>
 __global__ void __launch_bounds__(RED_BLOCK)
-k_maxerr_partial(LayoutDev l, const double *__restrict__ x, Geom g, F fn, Box box, double *part) {
+k_maxerr_partial(LayoutDev l, const double *__restrict__ x, G g, F fn, Box box, double *part) {
   const long long total = box.count();
   double m = 0.0;
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     int i0, i1, i2;
     unflatten(box, t, i0, i1, i2);
-    double px, py, pz;
-    point_position<CELL>(g, i0, i1, i2, px, py, pz);
-    m = fmax(m, fabs(x[lidx(l, i0, i1, i2)] - fn(px, py, pz)));
+    m = fmax(m, fabs(x[lidx(l, i0, i1, i2)] - eval_point<CELL>(g, fn, i0, i1, i2)));
   }
   const double r = block_reduce<true>(m);
   if (threadIdx.x == 0) part[blockIdx.x] = r;
@@ -198,15 +196,13 @@ __global__ void __launch_bounds__(RED_BLOCK) k_reduce_final(const double *part, 
 }
 
 // ---- analytic fills ---------------------------------------------------------------------------
-template <class F, bool CELL = false>
-__global__ void __launch_bounds__(256) k_fill_fn(LayoutDev l, double *x, Geom g, F fn, Box box) {
+template <class F, bool CELL = false, class G = Geom>
+__global__ void __launch_bounds__(256) k_fill_fn(LayoutDev l, double *x, G g, F fn, Box box) {
   const long long total = box.count();
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     int i0, i1, i2;
     unflatten(box, t, i0, i1, i2);
-    double px, py, pz;
-    point_position<CELL>(g, i0, i1, i2, px, py, pz);
-    x[lidx(l, i0, i1, i2)] = fn(px, py, pz);
+    x[lidx(l, i0, i1, i2)] = eval_point<CELL>(g, fn, i0, i1, i2);
   }
 }
 
@@ -216,16 +212,15 @@ struct FaceBoxes {
   int n;
 };
 
-template <class F>
-__global__ void __launch_bounds__(256) k_apply_dirichlet(LayoutDev l, double *x, Geom g, F fn, FaceBoxes fb) {
+template <class F, class G = Geom>
+__global__ void __launch_bounds__(256) k_apply_dirichlet(LayoutDev l, double *x, G g, F fn, FaceBoxes fb) {
   const long long total = fb.start[fb.n];
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     int f = 0;
     while (f + 1 < fb.n && t >= fb.start[f + 1]) ++f;
     int i0, i1, i2;
     unflatten(fb.box[f], t - fb.start[f], i0, i1, i2);
-    const double px = i0 * g.h0 + g.pb0, py = i1 * g.h1 + g.pb1, pz = i2 * g.h2 + g.pb2;
-    x[lidx(l, i0, i1, i2)] = fn(px, py, pz);
+    x[lidx(l, i0, i1, i2)] = eval_point<false>(g, fn, i0, i1, i2);
   }
 }
 
@@ -427,35 +422,63 @@ extern "C" int examg_add_scalar(const examg_layout_t *l_, double *x, double c, c
   return 0;
 }
 
-template <class F, bool CELL = false>
-static int max_err_impl(const char *who, const examg_layout_t *l_, const double *x, const examg_geom_t *g, const F &fn,
+// Do the node tables cover the box (and the upper node of every point's cell)?  The uniform formula covers every index.
+static inline bool geom_covers(const char *, const examg_geom_t *, const examg_layout_t *, const Box &) { return true; }
+static bool geom_covers(const char *who, const examg_grid_t *g, const examg_layout_t *l, const Box &b) {
+  const int bb[3] = {b.b0, b.b1, b.b2}, ee[3] = {b.e0, b.e1, b.e2};
+  if (g->ghost < 0) { set_error("%s: negative ghost count of the node tables", who); return false; }
+  for (int d = 0; d < 3; ++d) {
+    if (d >= l->nd) continue;
+    if (!g->nodes[d]) { set_error("%s: no node table of axis %d", who, d); return false; }
+    if (bb[d] + g->ghost < 0 || ee[d] + g->ghost + 1 > g->n[d]) {
+      set_error("%s: the node table of axis %d covers the points [%d, %d), the box needs [%d, %d)", who, d, -g->ghost, g->n[d] - g->ghost - 1, bb[d], ee[d]);
+      return false;
+    }
+  }
+  return true;
+}
+// a grid hands the kernels tables for the axes of the layout only
+static inline GridGeom make_geom_for(const examg_grid_t *g, const examg_layout_t *l) {
+  GridGeom q = make_geom(g);
+  if (l->nd < 3) q.n2 = nullptr;
+  if (l->nd < 2) q.n1 = nullptr;
+  return q;
+}
+static inline Geom make_geom_for(const examg_geom_t *g, const examg_layout_t *) { return make_geom(g); }
+
+template <class F, bool CELL = false, class GP = examg_geom_t>
+static int max_err_impl(const char *who, const examg_layout_t *l_, const double *x, const GP *g, const F &fn,
                         const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream) {
   if (!l_ || !x || !g || !begin || !end || !result || !work) { set_error("examg_max_err: null argument"); return 1; }
   const Box box = make_box(begin, end);
   hipStream_t s = (hipStream_t)stream;
   if (box.count() == 0) return check_hip(hipMemsetAsync(result, 0, sizeof(double), s), "examg_max_err memset");
   if (!box_inside(l_, box, 0)) { set_error("examg_max_err: box leaves the allocation"); return 1; }
+  if (!geom_covers(who, g, l_, box)) return 1;
   const int nb = red_blocks(box.count());
-  hipLaunchKernelGGL((k_maxerr_partial<F, CELL>), dim3(nb), dim3(RED_BLOCK), 0, s, make_layout(l_), x, make_geom(g), fn, box, (double *)work);
+  hipLaunchKernelGGL((k_maxerr_partial<F, CELL, decltype(make_geom_for(g, l_))>), dim3(nb), dim3(RED_BLOCK), 0, s, make_layout(l_), x, make_geom_for(g, l_), fn, box,
+                     (double *)work);
   hipLaunchKernelGGL((k_reduce_final<true>), dim3(1), dim3(RED_BLOCK), 0, s, (const double *)work, nb, result);
   EXAMG_CHECK_LAUNCH(who);
   return 0;
 }
 
-template <class F, bool CELL = false>
-static int fill_impl(const char *who, const examg_layout_t *l_, double *x, const examg_geom_t *g, const F &fn, const int32_t *begin,
+template <class F, bool CELL = false, class GP = examg_geom_t>
+static int fill_impl(const char *who, const examg_layout_t *l_, double *x, const GP *g, const F &fn, const int32_t *begin,
                      const int32_t *end, examg_stream_t stream) {
   if (!l_ || !x || !g || !begin || !end) { set_error("examg_fill: null argument"); return 1; }
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   if (!box_inside(l_, box, 0)) { set_error("examg_fill: box leaves the allocation"); return 1; }
-  hipLaunchKernelGGL((k_fill_fn<F, CELL>), grid_for(box.count()), dim3(256), 0, (hipStream_t)stream, make_layout(l_), x, make_geom(g), fn, box);
+  if (!geom_covers(who, g, l_, box)) return 1;
+  hipLaunchKernelGGL((k_fill_fn<F, CELL, decltype(make_geom_for(g, l_))>), grid_for(box.count()), dim3(256), 0, (hipStream_t)stream, make_layout(l_), x,
+                     make_geom_for(g, l_), fn, box);
   EXAMG_CHECK_LAUNCH(who);
   return 0;
 }
 
-template <class F>
-static int dirichlet_impl(const char *who, const examg_layout_t *l, double *x, const examg_geom_t *g, const F &fn, uint32_t face_mask,
+template <class F, class GP = examg_geom_t>
+static int dirichlet_impl(const char *who, const examg_layout_t *l, double *x, const GP *g, const F &fn, uint32_t face_mask,
                           examg_stream_t stream, bool tangential_ghost = true) {
   if (!l || !x || !g) { set_error("examg_apply_dirichlet: null argument"); return 1; }
   FaceBoxes fb;
@@ -476,12 +499,14 @@ static int dirichlet_impl(const char *who, const examg_layout_t *l, double *x, c
       }
       Box bx{b[0], b[1], b[2], e[0], e[1], e[2]};
       if (bx.count() == 0) continue;
+      if (!geom_covers(who, g, l, bx)) return 1;
       fb.box[fb.n] = bx;
       fb.start[fb.n + 1] = fb.start[fb.n] + bx.count();
       ++fb.n;
     }
   if (fb.n == 0) return 0;
-  hipLaunchKernelGGL((k_apply_dirichlet<F>), grid_for(fb.start[fb.n], 2048), dim3(256), 0, (hipStream_t)stream, make_layout(l), x, make_geom(g), fn, fb);
+  hipLaunchKernelGGL((k_apply_dirichlet<F, decltype(make_geom_for(g, l))>), grid_for(fb.start[fb.n], 2048), dim3(256), 0, (hipStream_t)stream, make_layout(l), x,
+                     make_geom_for(g, l), fn, fb);
   EXAMG_CHECK_LAUNCH(who);
   return 0;
 }
@@ -506,6 +531,37 @@ bool examg::expr_ok(const examg_expr_t *e) {
   }
   if (sp != 1) { set_error("examg expression: must leave exactly one value"); return false; }
   return true;
+}
+
+// the programs of the _grid entry points may also read the widths of the point's cell
+static bool expr_ok_grid(const examg_expr_t *e) {
+  if (!e || e->n < 1 || e->n > EXAMG_MAX_EXPR) { set_error("examg expression: null or too long"); return false; }
+  examg_expr_t q = *e;
+  for (int i = 0; i < q.n; ++i)
+    if (q.op[i] >= EXAMG_OP_WX && q.op[i] <= EXAMG_OP_WZ) q.op[i] = EXAMG_OP_X;      // an operand like the position
+  return expr_ok(&q);
+}
+static bool grid_layout_ok(const char *who, const examg_layout_t *l) {
+  if (l && l->transform != EXAMG_LAYOUT_PLAIN) { set_error("%s: a layout under a layout transformation", who); return false; }
+  return true;
+}
+
+extern "C" int examg_fill_expr_grid(const examg_layout_t *l, double *x, const examg_grid_t *g, const examg_expr_t *e, const int32_t *begin,
+                                    const int32_t *end, examg_stream_t stream) {
+  if (!expr_ok_grid(e) || !grid_layout_ok("examg_fill_expr_grid", l)) return 1;
+  return fill_impl<ExprEvalGrid, false, examg_grid_t>("examg_fill_expr_grid", l, x, g, ExprEvalGrid{*e}, begin, end, stream);
+}
+
+extern "C" int examg_apply_dirichlet_expr_grid(const examg_layout_t *l, double *x, const examg_grid_t *g, const examg_expr_t *e, uint32_t face_mask,
+                                               examg_stream_t stream) {
+  if (!expr_ok_grid(e) || !grid_layout_ok("examg_apply_dirichlet_expr_grid", l)) return 1;
+  return dirichlet_impl<ExprEvalGrid, examg_grid_t>("examg_apply_dirichlet_expr_grid", l, x, g, ExprEvalGrid{*e}, face_mask, stream);
+}
+
+extern "C" int examg_max_err_expr_grid(const examg_layout_t *l, const double *x, const examg_grid_t *g, const examg_expr_t *e, const int32_t *begin,
+                                       const int32_t *end, double *result, void *work, examg_stream_t stream) {
+  if (!expr_ok_grid(e) || !grid_layout_ok("examg_max_err_expr_grid", l)) return 1;
+  return max_err_impl<ExprEvalGrid, false, examg_grid_t>("examg_max_err_expr_grid", l, x, g, ExprEvalGrid{*e}, begin, end, result, work, stream);
 }
 
 extern "C" int examg_max_err_expr(const examg_layout_t *l_, const double *x, const examg_geom_t *g, const examg_expr_t *e,

@@ -59,6 +59,7 @@ from . import knowledge as _knowledge
 from .comm import Communicator
 from .domain import RectDomain
 from .field import Field, Stencil
+from .grid import CELL_VOLUME, AxisGrid, separate
 from .layout import FieldLayout
 from .exa4_parser import (Exa4SyntaxError, Exa4Unsupported, FunctionDecl, Parser, _COORD, _GRIDW, _MATH, _arith,  # noqa: F401
                           _colour_cond, _colour_expr, _conjuncts, _const_value, _contains, _find_calls, _has_coord, _lower_cond, _parity_expr, _walk)
@@ -112,6 +113,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             if d["num_blocks"] != (1, 1, 1) and d["frags_per_block"] == (1, 1, 1):
                 self._merged_blocks = (d["num_blocks"], d["frag_len"])      # what a per-process std::rand() needs to know (_exec_rand_fill)
         self.domain = domain
+        # node tables of an axis-aligned non-uniform grid (grid_isUniform = false, grid_spacingModel = "linearFct"); None: uniform
+        self.grid = AxisGrid.from_knowledge(self.k, self.nd, lo, hi, d["cells_per_dim_finest"], self.min_level, self.max_level,
+                                            blocks=domain.world_size, periodic=domain.periodic)
         self.comm = comm or Communicator(domain, ops)
         self.echo = echo
         self.out: List[str] = []
@@ -126,6 +130,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         self.fields: Dict[Tuple[str, int], Field] = {}
         self.stencils: Dict[Tuple[str, int], Stencil] = {}
         self.transfer: Dict[str, str] = {}
+        self.transfer_factor: Dict[str, float] = {}     # the common factor of a node restriction's weights: multiplies the statement's scale
         self._fn_cache: Dict[Tuple, Tuple] = {}
         self._rng = random.Random(20240229)
         self.fuse = fuse
@@ -205,6 +210,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             if ld.vec_len != 1 and fd.name not in sfield_fields:
                 raise Exa4Unsupported("vector-valued field %s outside a StencilField" % fd.name)
             if ld.localization == "Cell":
+                if self.grid is not None:
+                    raise Exa4Unsupported("field %s: cell-centred fields on a non-uniform grid" % fd.name)
                 self._declare_cell_field(fd, ld, nslots[fd.name], sfield_fields)
                 continue
             if self._bc_kind(fd.bc) is not None:
@@ -240,6 +247,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         for sd in a.stencils:
             if sd.transfer:
                 self.transfer[sd.name] = sd.transfer
+                self.transfer_factor[sd.name] = float(sd.transfer_factor)
         self._stencil_decls = {s.name: s for s in a.stencils if not s.transfer}
         for sf in a.sfields:
             sd = self._stencil_decls.get(sf.stencil)
@@ -469,9 +477,19 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
 
                 raise Exa4Unsupported("coefficient-expression stencil %s outside the forms %s" % (name, _FORMS))
             fr = _Frame(lvl, {})
+            if self.grid is not None and any(self._reads_grid(e) for _, e in sd.entries):
+                # entries over the virtual fields of a non-uniform grid: per-axis tables, allocated once per level (examg_axis_op)
+                s = self.stencils[(name, lvl)] = separate(name, sd.entries, self.nd, lvl, self.grid, lambda x: self._eval(x, fr))
+                s.c_struct(self.ops)      # the tables go to the device here, never inside a recording
+                return s
             offs = [tuple(o) + (0,) * (3 - len(o)) for o, _ in sd.entries]
             s = self.stencils[(name, lvl)] = Stencil(offs, [float(self._eval(e, fr)) for _, e in sd.entries])
         return s
+
+    @staticmethod
+    def _reads_grid(e) -> bool:
+        """Does the expression name a virtual field of the grid (a width, a position, the cell volume)?"""
+        return any(n and n[0] in ("id", "vfo") and isinstance(n[1], str) and n[1].startswith("vf_") for n in _walk(e))
 
     # -- analytic function recognition ----------------------------------------------------------------------------------
     def _point_eval(self, e, lvl: Optional[int], x: float, y: float, z: float):
@@ -508,13 +526,23 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             return self._compile_point_expr(e[1], lvl, subst) + [("neg", None)]
         if k == "fld" and subst is not None and "__u" in subst:
             return [("u", None)]          # the one field access of a coefficient expression: EXAMG_OP_U (exa4_nonlinear.py)
+        if k == "vfo":
+            raise Exa4Unsupported("point expression with the offset access %s@[...]" % e[1])
         if k == "id":
             name = e[1]
             if subst is not None and name in subst:
                 return list(subst[name])
             m = _COORD.match(name)
             if m:
+                if self.grid is not None and m.group(1).startswith("cellCent"):
+                    raise Exa4Unsupported("%s on a non-uniform grid" % name)
                 return [(m.group(2), None)]
+            if self.grid is not None and name == CELL_VOLUME:       # the product of the widths of the point's cell
+                prog = [("wx", None), ("wy", None), ("*", None)]
+                return prog + ([("wz", None), ("*", None)] if self.nd == 3 else [])
+            m = _GRIDW.match(name) if self.grid is not None else None
+            if m and m.group(1) == "cellWidth":
+                return [("w" + m.group(2), None)]
             return [("const", float(self._eval(e, fr)))]        # globals, PI, vf_gridWidth_*
         if k == "bin" and e[1] in ("+", "-", "*", "/"):
             return self._compile_point_expr(e[2], lvl, subst) + self._compile_point_expr(e[3], lvl, subst) + [(e[1], None)]
@@ -542,7 +570,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
     def _analytic(self, e, lvl: Optional[int]):
         """(fn id, params) of a built-in point function when the expression is one, else an expression program (ExprC)."""
         try:
-            return self._recognise(e, lvl)
+            if self.grid is None:         # the built-in point functions are functions of a uniform grid's positions
+                return self._recognise(e, lvl)
         except Exa4Unsupported:
             pass
         key = ("expr", repr(e), lvl)
@@ -586,7 +615,15 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                 return math.pi
             m = _GRIDW.match(name)
             if m:
+                if self.grid is not None:
+                    raise Exa4Unsupported("%s on a non-uniform grid%s" % (name, "" if m.group(1) == "gridWidth" else
+                                                                           " outside a stencil entry or a point expression"))
                 return self.domain.h(self._level_of(e[2], fr))["xyz".index(m.group(2))]
+            if name == CELL_VOLUME:       # uniform grid: the constant it is, the widths multiplied in axis order
+                if self.grid is not None:
+                    raise Exa4Unsupported("%s on a non-uniform grid outside a stencil entry or a point expression" % name)
+                h = self.domain.h(self._level_of(e[2], fr))
+                return h[0] * h[1] * h[2] if self.nd == 3 else (h[0] * h[1] if self.nd == 2 else h[0])
             m = _COORD.match(name)
             if m:
                 v = fr.vars.get("__" + m.group(2))
@@ -596,6 +633,11 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             raise Exa4SyntaxError("unknown name %r" % name)
         if k == "call":
             return self._call(e, fr)
+        if k == "vfo":
+            # a virtual field of the grid at a neighbouring cell: on a uniform grid widths and volumes are the constants they are
+            if self.grid is None and (e[1] == CELL_VOLUME or _GRIDW.match(e[1])):
+                return self._eval(("id", e[1], e[2]), fr)
+            raise Exa4Unsupported("%s@[...] outside an entry of a stencil over the grid's virtual fields" % e[1])
         if k in ("fld", "sten", "sentry"):
             raise Exa4Unsupported("field / stencil access %s outside a recognised loop body" % e[1])
         raise Exa4SyntaxError("expression %r" % (e,))
@@ -607,6 +649,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             if a[0] != "sten":
                 raise Exa4Unsupported("diag of a non-stencil")
             st = self.stencil(a[1], self._level_of(a[2], fr))
+            if getattr(st, "is_axis", False):
+                raise Exa4Unsupported("diag of a stencil over the grid's virtual fields outside the smoother forms ((1.0 / diag(A)) * omega), (omega / diag(A))")
             if st.cfield is not None:
                 raise Exa4Unsupported("diag of a stencil field outside the smoother form ((1.0 / diag(A)) * omega)")
             return st.diag
@@ -1110,7 +1154,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         mask = self.domain.face_mask()
         if mask:
             self.launches += 1
-            if isinstance(f.bc_fn, int):
+            if self.grid is not None:
+                self.ops.apply_dirichlet_expr_grid(f.lc, f.data(slot), self.grid.device(self.ops, f.level), f.bc_fn, mask)
+            elif isinstance(f.bc_fn, int):
                 self.ops.apply_dirichlet(f.lc, f.data(slot), self.domain.geom(f.level), f.bc_fn, f.bc_params, mask)
             else:
                 self.ops.apply_dirichlet_expr(f.lc, f.data(slot), self.domain.geom(f.level), f.bc_fn, mask)
@@ -1273,7 +1319,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                         fn, par = self._analytic(t[3][0][3], X.level)
                         for b, e in boxes:
                             self.launches += 1
-                            if isinstance(fn, int):
+                            if self.grid is not None:
+                                r = self.ops.max_err_expr_grid(X.lc, X.data(xs), self.grid.device(self.ops, X.level), fn, b, e)
+                            elif isinstance(fn, int):
                                 r = self.ops.max_err_fn(X.lc, X.data(xs), self.domain.geom(X.level), fn, par, b, e)
                             else:
                                 r = self.ops.max_err_expr(X.lc, X.data(xs), self.domain.geom(X.level), fn, b, e)
@@ -1286,6 +1334,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         """`A:[o] = expr` for every entry of a 7/5-entry stencil field: -div(a grad) with a at the half points."""
         name = body[0][2][1]
         lvl = self._level_of(body[0][2][2], fr)
+        if self.grid is not None:
+            raise Exa4Unsupported("initialisation of stencil field %s on a non-uniform grid" % name)
         A = self._stencil_planes(name, lvl)       # initialisation statements write the planes; loops get the transformed copy
         if A.cfield is None:
             raise Exa4Unsupported("%s is not a stencil field" % name)

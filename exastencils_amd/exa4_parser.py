@@ -3,7 +3,7 @@
 line ranges of the constructs covered).
 
 AST: tuples.  Expressions: ("num", v) ("str", s) ("id", name, level) ("fld", name, slot, level) ("sten", name, level)
-("sentry", name, level, offset) ("call", name, level, args) ("bin", op, a, b) ("neg", a) ("not", a).  Statements: ("decl", ..)
+("sentry", name, level, offset) ("vfo", name, level, offset) ("call", name, level, args) ("bin", op, a, b) ("neg", a) ("not", a).  Statements: ("decl", ..)
 ("assign", op, lhs, rhs) ("loop", target, only, where, reduction, body) ("comm", phase, what, target) ("applybc", target)
 ("advance", target) ("repeat", n, counter, body) ("until", cond, body) ("if", cond, then, else) ("color", exprs, body)
 ("levelscope", levels, body) ("return", expr) ("callstmt", call) ("repeatwith", conditions, body) ("solve", jacobi, relax, rows of (unknown, lhs, rhs)).  Level specifications: ("single", base, delta) ("all",)
@@ -90,6 +90,7 @@ class StencilDecl:
     levels: object
     entries: List[Tuple[Tuple[int, ...], object]] = _dcf(default_factory=list)   # (offset, coefficient expression)
     transfer: Optional[str] = None      # 'restriction' | 'prolongation'
+    transfer_factor: float = 1.0        # the common factor on the weights of a node restriction (examg_restrict's scale)
 
 
 @dataclass
@@ -118,6 +119,7 @@ _MATH = {"sqrt": math.sqrt, "fabs": abs, "abs": abs, "sin": math.sin, "cos": mat
          "asin": math.asin, "acos": math.acos, "atan": math.atan, "atan2": math.atan2, "log10": math.log10}
 _COORD = re.compile(r"^vf_(nodePosition|nodePos|boundaryCoord|boundaryPosition|boundaryPos|cellCenter|cellCentre)_([xyz])$")
 _GRIDW = re.compile(r"^vf_(gridWidth|cellWidth)_([xyz])$")
+_CELLVOL = "vf_cellVolume"
 
 
 # =====================================================================================================================
@@ -327,7 +329,7 @@ class Parser:
                 mapped.append((src, self.expr()))
             self.accept(",")
         if mapped:
-            d.transfer = _classify_transfer(mapped)
+            d.transfer, d.transfer_factor = _classify_transfer(mapped, with_factor=True)
         self.stencils.append(d)
 
     def _stencil_field(self):
@@ -707,6 +709,10 @@ class Parser:
             self.next()
             level = self._level_item()
         if self.at("@") and self.at("[", 1):
+            if name.startswith("vf_") and name not in self.field_names:
+                # a virtual field of the grid at a neighbouring cell / node: `vf_cellWidth_x@[-1, 0, 0]` (grid/l4/L4_VirtualFieldAccess.scala)
+                self.next()
+                return ("vfo", name, level, tuple(int(_const_value(e)) for e in self._const_list()))
             raise Exa4Unsupported("line %d: offset access %s@[...]" % (t.line, name))
         if name in self.field_names:
             return ("fld", name, slot, level)
@@ -784,8 +790,12 @@ def _arith(op: str, a, b):
     raise Exa4SyntaxError("operator %r" % op)
 
 
-def _classify_transfer(mapped) -> str:
+def _classify_transfer(mapped, with_factor: bool = False):
     """`[i0, i1] from [2.0 * i0 - 1.0, ...] with w` entries: which inter-grid operator, and is it the linear one?
+    with_factor: (kind, factor) -- the linear NODE RESTRICTION may carry one common factor on all its weights
+    (Examples/Poisson/2D_FV_Poisson_fromL4.exa4:53-63, `NodeRestrictionForRes`: the finite-volume residual is an integral over the
+    control volume, 2^d times the linear weights); the factor is the `scale` of examg_restrict.  Every other operator with a factor is
+    refused as before, and so is a factored restriction when the caller does not ask for the factor.
     Node: 3^d entries, offsets in {-1, 0, 1} (restriction, weights kron [1/4 1/2 1/4]) or {-1/2, 0, 1/2} (prolongation, kron
     [1/2 1 1/2]).  Cell (operator/l4/L4_DefaultRestriction.scala:37-43): 2^d entries, offsets 2i + {0, 1} and weights 0.5^d
     (restriction: 'cell_restriction'), or the transpose times 2^d, offsets i/2 - {0, 1/2} and weights 1.0 ('cell_prolongation')."""
@@ -800,17 +810,24 @@ def _classify_transfer(mapped) -> str:
         want = 1.0 if prolong else 0.5 ** nd
         if not ok or any(w != want for w in weights):
             raise Exa4Unsupported("inter-grid stencil is not the linear cell %s" % ("prolongation" if prolong else "restriction"))
-        return "cell_prolongation" if prolong else "cell_restriction"
+        kind = "cell_prolongation" if prolong else "cell_restriction"
+        return (kind, 1.0) if with_factor else kind
     if len(offs) != 3 ** nd:
         raise Exa4Unsupported("inter-grid stencil with %d entries in %dD" % (len(offs), nd))
+    factor = 1.0
+    if with_factor and not prolong:
+        centre = [w for off, w in zip(offs, weights) if all(o == 0.0 for o in off)]
+        if len(centre) == 1 and centre[0] != 0.0:
+            factor = centre[0] / 0.5 ** nd        # exact for every factor 2^k
     for off, w in zip(offs, weights):
         want = 1.0
         for o in off:
             far = (abs(o) == 0.5) if prolong else (abs(o) == 1.0)
             want *= (0.5 if far else 1.0) if prolong else (0.25 if far else 0.5)
-        if abs(w - want) > 1e-15:
+        if abs(w - factor * want) > 1e-15 * max(1.0, abs(factor)):
             raise Exa4Unsupported("inter-grid stencil is not the linear %s" % ("prolongation" if prolong else "restriction"))
-    return "prolongation" if prolong else "restriction"
+    kind = "prolongation" if prolong else "restriction"
+    return (kind, factor) if with_factor else kind
 
 
 

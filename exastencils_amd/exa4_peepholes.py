@@ -330,8 +330,8 @@ class Peepholes:
         solver generator writes (Function VCycle_0@coarsest, Testing/Smoothers/Jac.exa4:75-109): alpha = res * res / alphaDenom
         with the norm carried over instead of a sum of squares, both vector updates in one loop, no `apply bc` statements, the
         solution possibly slotted (accessed through <active> only)."""
-        if self.domain.world_size != 1 or not hasattr(self.ops, "cg_coarse"):
-            return None
+        if self.domain.world_size != 1 or not hasattr(self.ops, "cg_coarse") or self.grid is not None:
+            return None         # a non-uniform grid: the solver's statements run one by one (table stencils, table boundary values)
         if self.domain.face_mask() != (1 << (2 * self.nd)) - 1:
             return None         # a periodic block is its own neighbour: the solver's `communicate` statements do something
         body = self._inline(fn.body, lvl)

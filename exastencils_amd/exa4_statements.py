@@ -13,7 +13,7 @@ from dataclasses import dataclass
 from typing import Optional
 
 from .exa4_common import APPLY, RESIDUAL, SMOOTH, _Frame
-from .exa4_parser import Exa4Unsupported, _contains, _has_coord
+from .exa4_parser import Exa4Unsupported, _contains, _has_coord, _walk
 from .field import Field, Stencil
 
 
@@ -21,7 +21,7 @@ from .field import Field, Stencil
 class LoopStmt:
     """What one assignment in a loop body launches.  kind: set | fill_fn | fill_expr | fill_expr_cell | copy | axpby | add_scalar |
     residual | apply | smooth | restrict | restrict_cell | prolong_add | prolong_add_cell | sys_row | pointwise_mul | pointwise_sub |
-    nl_op | nl_smooth."""
+    nl_op | nl_smooth | axis_residual | axis_apply | axis_smooth."""
     kind: str
     D: Field                        # the field assigned to
     ds: int
@@ -43,7 +43,11 @@ class SmootherRefused(Exa4Unsupported):
 class Statements:
     # pattern helpers ---------------------------------------------------------------------------------------------------
     def _is_scalar(self, e) -> bool:
-        return not _contains(e, ("fld", "sten", "sentry")) and not _has_coord(e, self.functions)
+        return not _contains(e, ("fld", "sten", "sentry")) and not self._over_position(e)
+
+    def _over_position(self, e) -> bool:
+        """Does the expression depend on the point: a coordinate, or -- on a non-uniform grid -- a width or the volume of its cell?"""
+        return _has_coord(e, self.functions) or (self.grid is not None and self._reads_grid(e))
 
     def _same_access(self, a, b, fr: _Frame) -> bool:
         if a[0] != "fld" or b[0] != "fld":
@@ -62,7 +66,8 @@ class Statements:
         if s[0] != "sten":
             return None
         if s[1] in self.transfer:
-            return scale, self.transfer[s[1]], s[1], None, e[3]
+            factor = self.transfer_factor.get(s[1], 1.0)
+            return (scale if factor == 1.0 else scale * factor), self.transfer[s[1]], s[1], None, e[3]
         return scale, "stencil", self.stencil(s[1], self._level_of(s[2], fr)), None, e[3]
 
     def _residual_form(self, e, fr: _Frame):
@@ -78,7 +83,8 @@ class Statements:
         """(omega, stencil as the kernel needs it): a stencil field carries the FORM of the weight -- the kernels evaluate per point
         what the statement says, `(1.0 / diag(A)) * omega` (Testing/SISC/3D_VarCoeff.exa4:145) or `omega / diag(A)`
         (Testing/PolyExpl/RBGS3Dvc.exa4:52); the two round differently."""
-        if A.cfield is None:
+        axis = getattr(A, "is_axis", False)
+        if A.cfield is None and not axis:
             return float(self._eval(w, fr)), A
         if (w[0] == "bin" and w[1] == "*" and w[2][0] == "bin" and w[2][1] == "/" and w[2][2] == ("num", 1.0)
                 and w[2][3][0] == "call" and w[2][3][1] == "diag" and self._is_scalar(w[3])):
@@ -86,11 +92,34 @@ class Statements:
         if w[0] == "bin" and w[1] == "/" and w[3][0] == "call" and w[3][1] == "diag" and self._is_scalar(w[2]):
             import dataclasses
 
-            return float(self._eval(w[2], fr)), dataclasses.replace(A, wform=1)
-        raise Exa4Unsupported("smoother weight on a stencil field must read ((1.0 / diag(A)) * omega) or (omega / diag(A))")
+            return float(self._eval(w[2], fr)), (A.with_wform(1) if axis else dataclasses.replace(A, wform=1))
+        raise Exa4Unsupported("smoother weight on a stencil %s must read ((1.0 / diag(A)) * omega) or (omega / diag(A))"
+                              % ("over the grid's virtual fields" if axis else "field"))
 
     # -- the recogniser -------------------------------------------------------------------------------------------------
     def _recognise_assign(self, st, fr: _Frame, colour=None) -> LoopStmt:
+        """_recognise_plain, and the one thing that holds for every form: a stencil over the virtual fields of a non-uniform grid
+        (grid.AxisStencil) stands in the three stencil loops only, which become kinds of their own -- no peephole, no fusion, no
+        one-kernel solver and no coloured or lexicographic sweep asks for them; each runs as one examg_axis_op."""
+        import dataclasses
+
+        if self.grid is not None:
+            for n in _walk(st[3]):
+                sd = self._stencil_decls.get(n[1]) if n and n[0] == "sten" else None
+                if sd is not None and any(self._reads_grid(e) and _contains(e, ("fld",)) for _, e in sd.entries):
+                    raise Exa4Unsupported("stencil %s: a field in an entry of a stencil over the grid's virtual fields" % n[1])
+        k = self._recognise_plain(st, fr, colour)
+        if k.A is not None and getattr(k.A, "is_axis", False):
+            if k.kind not in ("residual", "apply", "smooth"):
+                raise Exa4Unsupported("a stencil over the grid's virtual fields in a %s statement" % k.kind)
+            for X in (k.D, k.U, k.F):
+                if X is not None and (X.layout.is_cell or X.layout.transform):
+                    raise Exa4Unsupported("a stencil over the grid's virtual fields on the %s field %s"
+                                          % ("cell" if X.layout.is_cell else "colour-split", X.name))
+            return dataclasses.replace(k, kind="axis_" + k.kind)
+        return k
+
+    def _recognise_plain(self, st, fr: _Frame, colour=None) -> LoopStmt:
         """The record of the assignment `st` of a loop body, or the refusal that names why it is none of the kernels.  Scalars are
         evaluated here; nothing is launched or counted.  `colour`: the red-black colour of the loop, for the forms whose refusals
         depend on it (system rows, semilinear operators); what a smoother needs of it is checked where it is launched."""
@@ -102,7 +131,7 @@ class Statements:
             return self._recognise_nonlinear(op, lhs, rhs, D, ds, colour, fr)
         if op == "=":
             if not _contains(rhs, ("fld", "sten", "sentry")):        # a scalar, or an expression over the position
-                if not _has_coord(rhs, self.functions):
+                if not self._over_position(rhs):
                     return LoopStmt("set", D, ds, s=float(self._eval(rhs, fr)))
                 if D.layout.is_cell:
                     return LoopStmt("fill_expr_cell", D, ds, prog=self._cell_program(rhs, D.level))
@@ -230,15 +259,25 @@ class Statements:
                 return
             if not in_place and colour is not None:
                 raise Exa4Unsupported("coloured update into another slot")
+        if kind == "axis_smooth":
+            in_place = D is U and k.ds == k.us
+            if in_place != (colour is not None):
+                raise Exa4Unsupported("a smoother over the grid's virtual fields runs out of place, or in place under the red-black colouring")
         self.launches += 1
         if kind == "set":
             ops.set(D.lc, d, k.s, b, e)
+        elif kind in ("axis_residual", "axis_apply", "axis_smooth"):
+            mode = {"axis_residual": RESIDUAL, "axis_apply": APPLY, "axis_smooth": SMOOTH}[kind]
+            ops.axis_op(mode, U.lc, u, lf, f, D.lc, d, k.A, k.s, colour if kind == "axis_smooth" and colour is not None else -1, b, e)
         elif kind == "fill_expr_cell":
             ops.fill_expr_cell(D.lc, d, self.domain.geom(D.level), k.prog, b, e)
         elif kind == "fill_fn":
             ops.fill_fn(D.lc, d, self.domain.geom(D.level), k.prog[0], k.prog[1], b, e)
         elif kind == "fill_expr":
-            ops.fill_expr(D.lc, d, self.domain.geom(D.level), k.prog, b, e)
+            if self.grid is not None:
+                ops.fill_expr_grid(D.lc, d, self.grid.device(ops, D.level), k.prog, b, e)
+            else:
+                ops.fill_expr(D.lc, d, self.domain.geom(D.level), k.prog, b, e)
         elif kind in ("copy", "axpby"):
             ops.axpby(U.lc, u, D.lc, d, k.s, k.t, b, e)
         elif kind == "add_scalar":
@@ -283,6 +322,8 @@ class Statements:
         for X in (D, F, U) if k.kind == "residual" else (D, U, F):      # in the order the statement names them
             if X is not None and X.layout.transform:
                 raise Exa4Unsupported("colour-split field %s %s" % (X.name, what))
+        if k.kind.startswith("axis_"):
+            raise Exa4Unsupported("a stencil over the grid's virtual fields %s" % what)
         if k.kind not in ("smooth", "residual", "apply"):
             return False
         # a loop that reads the array it writes: only where no point of the colour is a neighbour of another one

@@ -68,7 +68,7 @@ class Systems:
             if lap is not None or not all(self._is_scalar(x) for x in scal):
                 return None
             A = self.stencil(stens[0][1], self._level_of(stens[0][2], fr))
-            if A.cfield is not None:      # refused below, once the expression has shown itself to be a system row
+            if A.cfield is not None or getattr(A, "is_axis", False):      # refused below, once the expression has shown itself to be a system row
                 lap = (A, fac[-1], stens[0][1])
                 continue
             s = None

@@ -36,9 +36,30 @@ class GeomC(C.Structure):
     _fields_ = [("pos_begin", C.c_double * 3), ("h", C.c_double * 3)]
 
 
+class GridC(C.Structure):
+    """examg_grid_t: the node tables of an axis-aligned grid on the device; element j of a table is node j - ghost."""
+    _fields_ = [("nodes", C.c_void_p * 3), ("n", C.c_int32 * 3), ("ghost", C.c_int32)]
+
+
 class ColouringC(C.Structure):
     """examg_colouring_t: 1 to 3 colour expressions (shift + sum of the axes' indices) % mod and the remainders of one colour."""
     _fields_ = [("nexpr", C.c_int32)] + [(n, C.c_int32 * 3) for n in ("axes", "shift", "mod", "rem")]
+
+
+AXIS_MAX_TERMS = 32
+AXIS_AUTO, AXIS_GENERIC, AXIS_STAR = 0, 1, 2      # examg_axis_stencil_t.route, and what examg_axis_route answers
+
+
+class AxisTermC(C.Structure):
+    """examg_axis_term_t: X[tab[0]][i0] * ((s * Z[tab[2]][i2]) * Y[tab[1]][i1]); tab[d] = -1: no table of that axis."""
+    _fields_ = [("entry", C.c_int32), ("tab", C.c_int32 * 3), ("s", C.c_double)]
+
+
+class AxisStencilC(C.Structure):
+    """examg_axis_stencil_t: a stencil whose coefficients are sums of products of per-axis tables (include/examg.h)."""
+    _fields_ = [("nent", C.c_int32), ("diag", C.c_int32), ("off", (C.c_int32 * 3) * MAXE), ("wform", C.c_int32), ("nterm", C.c_int32),
+                ("term", AxisTermC * AXIS_MAX_TERMS), ("tables", C.c_void_p * 3), ("ntab", C.c_int32 * 3), ("tab_begin", C.c_int32 * 3),
+                ("tab_len", C.c_int32 * 3), ("route", C.c_int32)]
 
 
 SYS_MAX = 3
@@ -54,6 +75,8 @@ class SysC(C.Structure):
 MAX_EXPR = 256
 OPS = {"const": 0, "x": 1, "y": 2, "z": 3, "+": 4, "-": 5, "*": 6, "/": 7, "neg": 8, "sin": 9, "cos": 10, "exp": 11, "sinh": 12,
        "cosh": 13, "sqrt": 14, "pow": 15, "tan": 16, "log": 17, "fabs": 18, "max": 19, "min": 20, "tanh": 21}
+# ... and the widths of the point's cell, which the _grid entry points know beside them (every other entry point refuses them)
+GRID_OPS = dict(OPS, wx=23, wy=24, wz=25)
 
 
 class ExprC(C.Structure):
@@ -68,7 +91,7 @@ class ExprC(C.Structure):
         e = ExprC()
         e.n = len(prog)
         for i, (name, c) in enumerate(prog):
-            e.op[i] = OPS[name]
+            e.op[i] = GRID_OPS[name]
             e.c[i] = float(c) if c is not None else 0.0
         e.program = list(prog)
         return e
@@ -129,6 +152,7 @@ SYMBOLS = [
     "examg_sys_op", "examg_sys_relax", "examg_pointwise_mul",
     "examg_nl_op", "examg_nl_smooth",
     "examg_gs_sweep", "examg_gs_route",
+    "examg_axis_op", "examg_axis_route", "examg_fill_expr_grid", "examg_apply_dirichlet_expr_grid", "examg_max_err_expr_grid",
 ]
 
 COMM_ID_BYTES = 128
@@ -261,6 +285,13 @@ def load(path=None):
     L.examg_nl_smooth.argtypes = [lp, vp, lp, vp, lp, vp, sp, np_, np_, C.c_double, C.c_int, ip, ip, vp]
     L.examg_gs_sweep.argtypes = [lp, vp, lp, vp, sp, C.c_double, ip, ip, vp]
     L.examg_gs_route.argtypes = [lp, lp, sp, ip, ip]
+    ap = C.POINTER(AxisStencilC)
+    L.examg_axis_op.argtypes = [C.c_int, lp, vp, lp, vp, lp, vp, ap, C.c_double, C.c_int, ip, ip, vp]
+    L.examg_axis_route.argtypes = [C.c_int, lp, lp, lp, ap, C.c_int, ip, ip]
+    rp = C.POINTER(GridC)
+    L.examg_fill_expr_grid.argtypes = [lp, vp, rp, ep, ip, ip, vp]
+    L.examg_apply_dirichlet_expr_grid.argtypes = [lp, vp, rp, ep, C.c_uint32, vp]
+    L.examg_max_err_expr_grid.argtypes = [lp, vp, rp, ep, ip, ip, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("examg_version", "examg_last_error", "examg_device_count", "examg_reduce_work_bytes", "examg_exchange_workspace_bytes",

@@ -447,6 +447,30 @@ int examg_fill_dup_faces_expr(const examg_layout_t *l, double *x, const examg_ge
 int examg_max_err_expr(const examg_layout_t *l, const double *x, const examg_geom_t *g, const examg_expr_t *e,
                        const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream);
 
+/* ---- the same three over the node tables of an axis-aligned, non-uniform grid (grid_isUniform = false, grid_isAxisAligned = true;
+ * grid/ir/IR_SetupNodePositions.scala).  examg_grid_t: per axis d of the layout a DEVICE array nodes[d] of n[d] node positions; element j
+ * is the position of the node with iterator index j - ghost (ghost nodes of the table in front).  The position of point i is
+ * nodes[d][i_d + ghost]; programs may also read the width of the point's cell, nodes[d][i_d + ghost + 1] - nodes[d][i_d + ghost], through
+ * EXAMG_OP_WX / WY / WZ (`vf_cellWidth_*`; `vf_cellVolume` is their product, spelt out by the caller).  On an axis the layout does not have,
+ * position and width are 0.0.  Otherwise the arithmetic, the boxes and the faces are those of examg_fill_expr, examg_apply_dirichlet_expr
+ * and examg_max_err_expr -- one kernel each, instantiated for the two kinds of geometry.  The width opcodes are refused by every entry
+ * point that takes an examg_geom_t.  Refused before anything is launched: a box (a face, its tangential ghost range included) with a point
+ * whose node or whose cell's upper node the table does not hold; a layout under a layout transformation. */
+#define EXAMG_OP_WX 23
+#define EXAMG_OP_WY 24
+#define EXAMG_OP_WZ 25
+typedef struct examg_grid {
+  const double *nodes[3];
+  int32_t n[3];
+  int32_t ghost;
+} examg_grid_t;
+int examg_fill_expr_grid(const examg_layout_t *l, double *x, const examg_grid_t *g, const examg_expr_t *e, const int32_t *begin,
+                         const int32_t *end, examg_stream_t stream);
+int examg_apply_dirichlet_expr_grid(const examg_layout_t *l, double *x, const examg_grid_t *g, const examg_expr_t *e, uint32_t face_mask,
+                                    examg_stream_t stream);
+int examg_max_err_expr_grid(const examg_layout_t *l, const double *x, const examg_grid_t *g, const examg_expr_t *e, const int32_t *begin,
+                            const int32_t *end, double *result, void *work, examg_stream_t stream);
+
 /* ---- stencil-field initialisation.  Testing/SISC/3D_VarCoeff.exa4:206-217 (2*nd+1 entries): -div(a grad u) with the
  * coefficient expression `a` evaluated half a mesh width to either side of the node.  With (x, y, z) the node position
  * (index * h + pos_begin) and, per dimension d, ap_d = a(position + (0.5 * h_d) in d), am_d = a(position - (0.5 * h_d) in d):
@@ -822,6 +846,72 @@ int examg_nl_op(int mode, const examg_layout_t *lu, const double *u, const examg
 int examg_nl_smooth(const examg_layout_t *lu, const double *u_in, const examg_layout_t *ld, double *u_out, const examg_layout_t *lf,
                     const double *rhs, const examg_stencil_t *st, const examg_nlexpr_t *c, const examg_nlexpr_t *d, double w, int colour,
                     const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
+/* ---- Table-coefficient stencils: operators on axis-aligned non-uniform grids ------------------------------------------------
+ * `grid_isUniform = false, grid_isAxisAligned = true` (grid/ir/IR_SetupNodePositions.scala): the node positions are one table per axis,
+ * and a stencil written over the virtual fields of the grid (`vf_cellWidth_x@[-1, 0, 0]`, Examples/Poisson/3D_FV_Poisson_fromL4.exa4:39-58)
+ * depends on the position through one-dimensional tables only.  The host separates every entry into TERMS
+ *     c_t(i) = X_t[i0] * ((s_t * Z_t[i2]) * Y_t[i1])
+ * s_t a scalar, X_t / Y_t / Z_t tables over the iterator index of one axis; an absent table (tab[d] = -1) is the factor 1.0, and Z is
+ * absent in 2-D.  The kernels form the coefficients of a point from the tables: u, rhs and dst are the only streams (24 B per point
+ * where a 7-entry stencil field streams 80 B).
+ *
+ * examg_axis_stencil_t:
+ *   nent, diag, off   the entries as in examg_stencil_t; every offset in {-1, 0, 1}, diag names the (0,0,0) entry
+ *   wform             EXAMG_WEIGHT_INV_TIMES / EXAMG_WEIGHT_DIVIDE: how the smoother statement writes its weight (as for a stencil field)
+ *   nterm, term[]     1 .. EXAMG_AXIS_MAX_TERMS terms, SORTED BY ENTRY, every entry with at least one; term[t].tab[d] is the index of a
+ *                     table of axis d or -1
+ *   tables[d]         device array of ntab[d] tables of tab_len[d] doubles each (table k at tables[d] + k * tab_len[d]); element j of
+ *                     a table belongs to the iterator index tab_begin[d] + j
+ *   route             EXAMG_AXIS_AUTO, or one of the two kernels by name (below)
+ *
+ * examg_axis_op: the three loop kinds of examg_stencil_op (EXAMG_APPLY, EXAMG_RESIDUAL, EXAMG_SMOOTH) on [begin, end).  Arithmetic, fp64,
+ * no contraction, per point:
+ *   term         c_t = X_t[i0] * ((s_t * Z_t[i2]) * Y_t[i1])
+ *   coefficient  c_k = the terms of entry k folded left to right in declared order (c_t0, then + c_t1, ..)
+ *   convolution  acc = c_0 * u(i + o_0), then acc + c_k * u(i + o_k) in entry order
+ *   APPLY dst = acc;  RESIDUAL dst = rhs - acc;  SMOOTH dst = u + ww * (rhs - acc), ww = (1.0 / c_diag) * w or w / c_diag as wform names
+ * -- from the coefficients on exactly what examg_stencil_op computes for a stencil field in planes that holds the c_k.  colour -1: all
+ * points; 0 / 1: the points with (i0 + i1 + i2) % 2 == colour.  dst may be u only when colour >= 0.  Every argument through its own
+ * layout; only the points of the box (of the colour) are written, in dst alone.
+ * Refused, before anything is launched (non-zero, examg_last_error): a box with an index that a table of a used axis does not cover; a
+ * box whose one-point shell leaves the u allocation, or that leaves the dst / rhs allocation; a layout under a layout transformation;
+ * layouts that are not 2-D or 3-D or differ in dimensionality; offsets outside {-1, 0, 1}; terms not sorted by entry, an entry without
+ * a term, a table index outside the axis's tables; dst == u without a colour.  An empty box is a no-op that returns 0.  Nothing is
+ * allocated; the launches are capturable.
+ *
+ * Two kernels, the same bits.  EXAMG_AXIS_GENERIC: any stencil, one lane per point, the X table windows and the row products
+ * (s * Z) * Y of a workgroup's rows staged in LDS.  EXAMG_AXIS_STAR: 3-D stencils of the centre and the six axis neighbours (each once,
+ * in any order) with at most 12 terms; two x points per lane, z march with u[z-1], u[z], u[z+1] in registers, the X tables of the
+ * wave's 128-point window in registers, the row products wave-uniform.  Eligibility depends on the stencil's shape alone, never on the
+ * size of the box.  st->route = EXAMG_AXIS_AUTO takes the star kernel where it is eligible; EXAMG_AXIS_STAR on any other stencil is an
+ * error.  examg_axis_route answers what examg_axis_op would do with these arguments, nothing launched: -1 refused (error text set),
+ * 0 empty box, EXAMG_AXIS_GENERIC or EXAMG_AXIS_STAR. */
+#define EXAMG_AXIS_MAX_TERMS 32
+enum { EXAMG_AXIS_AUTO = 0, EXAMG_AXIS_GENERIC = 1, EXAMG_AXIS_STAR = 2 };
+typedef struct examg_axis_term {
+  int32_t entry;
+  int32_t tab[3];
+  double s;
+} examg_axis_term_t;
+typedef struct examg_axis_stencil {
+  int32_t nent;
+  int32_t diag;
+  int32_t off[EXAMG_MAX_ENTRIES][3];
+  int32_t wform;
+  int32_t nterm;
+  examg_axis_term_t term[EXAMG_AXIS_MAX_TERMS];
+  const double *tables[3];
+  int32_t ntab[3];
+  int32_t tab_begin[3];
+  int32_t tab_len[3];
+  int32_t route;
+} examg_axis_stencil_t;
+int examg_axis_op(int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs, const examg_layout_t *ld,
+                  double *dst, const examg_axis_stencil_t *st, double w, int colour, const int32_t *begin, const int32_t *end,
+                  examg_stream_t stream);
+int examg_axis_route(int mode, const examg_layout_t *lu, const examg_layout_t *lf, const examg_layout_t *ld, const examg_axis_stencil_t *st,
+                     int colour, const int32_t *begin, const int32_t *end);
 
 #ifdef __cplusplus
 }

@@ -43,6 +43,8 @@ __global__ void __launch_bounds__(256) k_apply_bc_cell(LayoutDev l, double *x, G
     double v;
     if (KIND == EXAMG_BC_NEUMANN) {
       v = interior;
+    } else if (KIND == EXAMG_BC_NEGATE) {
+      v = -interior;
     } else {
       // face centre: cell centres tangentially, the node position of the face (index 0 / inner) in the normal dimension
       double p[3];
@@ -176,7 +178,7 @@ extern "C" int examg_debug_cell_narrow(int on) {
 extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
                                    uint32_t face_mask, examg_stream_t stream) {
   if (!l || !x || !g) { set_error("examg_apply_bc_cell: null argument"); return 1; }
-  if (kind != EXAMG_BC_DIRICHLET && kind != EXAMG_BC_NEUMANN) { set_error("examg_apply_bc_cell: unknown kind %d", kind); return 1; }
+  if (kind != EXAMG_BC_DIRICHLET && kind != EXAMG_BC_NEUMANN && kind != EXAMG_BC_NEGATE) { set_error("examg_apply_bc_cell: unknown kind %d", kind); return 1; }
   if (kind == EXAMG_BC_DIRICHLET && !expr_ok(expr)) return 1;
   if (!cell_layout_ok("examg_apply_bc_cell", l)) return 1;
   CellFaces fc;
@@ -206,12 +208,12 @@ extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const exa
     }
   if (fc.n == 0) return 0;
   examg_expr_t none;
-  if (kind == EXAMG_BC_NEUMANN) {
+  if (kind != EXAMG_BC_DIRICHLET) {
     none.n = 1;
     none.op[0] = EXAMG_OP_CONST;
     none.c[0] = 0.0;
   }
-  const ExprEval fn{kind == EXAMG_BC_NEUMANN ? none : *expr};
+  const ExprEval fn{kind != EXAMG_BC_DIRICHLET ? none : *expr};
   const int3 inner = make_int3(l->inner[0], l->inner[1], l->inner[2]);
   const long long total = fc.start[fc.n];
   long long nb = (total + 255) / 256;
@@ -219,6 +221,8 @@ extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const exa
   hipStream_t s = (hipStream_t)stream;
   if (kind == EXAMG_BC_NEUMANN)
     hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_NEUMANN>), dim3((unsigned)nb), dim3(256), 0, s, make_layout(l), x, make_geom(g), fn, fc, inner);
+  else if (kind == EXAMG_BC_NEGATE)
+    hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_NEGATE>), dim3((unsigned)nb), dim3(256), 0, s, make_layout(l), x, make_geom(g), fn, fc, inner);
   else
     hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_DIRICHLET>), dim3((unsigned)nb), dim3(256), 0, s, make_layout(l), x, make_geom(g), fn, fc, inner);
   EXAMG_CHECK_LAUNCH("k_apply_bc_cell");

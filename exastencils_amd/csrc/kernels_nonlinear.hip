@@ -15,27 +15,9 @@
 // the stack and seven below it) selected by the uniform stack pointer through scalar branches -- never an indexed array, so nothing
 // goes to scratch (private segment 0 in the code-object metadata of every instantiation; 156-169 VGPRs, no spills).
 #include "examg_common.h"
+#include "nl_program.h"      // NlProg, pack_program, nl_eval<R>: the interpreter the flux kernels share
 
 namespace examg {
-
-// A program as the kernel takes it: the opcodes packed eight to a 64-bit word (four scalar register pairs hold a whole program: the
-// dispatch loop reads no memory), the literals of its CONST instructions in order of appearance.
-struct NlProg {
-  int n, nconst;
-  unsigned long long w[EXAMG_MAX_NL_EXPR / 8];
-  double pool[EXAMG_MAX_NL_EXPR + 1];
-};
-
-static inline NlProg pack_program(const examg_nlexpr_t *e) {
-  NlProg p;
-  memset(&p, 0, sizeof(p));
-  p.n = e->n;
-  for (int i = 0; i < e->n; ++i) {
-    p.w[i >> 3] |= (unsigned long long)(e->op[i] & 255) << (8 * (i & 7));
-    if (e->op[i] == EXAMG_OP_CONST) p.pool[p.nconst++] = e->c[i];
-  }
-  return p;
-}
 
 struct NlArgs {
   LayoutDev lu, lq, lf, ld;
@@ -53,84 +35,6 @@ struct NlArgs {
 };
 
 enum { NL_SMOOTH = 3 };              // beside EXAMG_NL_APPLY / RESIDUAL / ADD
-
-// A program on R values per lane at once (R = 1: the gather kernel; the row-marching kernel interprets every instruction once for the R
-// rows a lane holds).  sp counts the values on the stack; the top one is t, the ones below s0 (bottom) .. s6.  The literal of the
-// next CONST instruction is fetched one instruction ahead (cnext), so its scalar load is in flight while the instructions before it
-// execute.
-#define NL_R(stmt) _Pragma("unroll") for (int r = 0; r < R; ++r) { stmt; }
-template <int R>
-__device__ __forceinline__ void nl_eval(const NlProg &e, const double (&v)[R], double (&res)[R]) {
-  double t[R], s0[R], s1[R], s2[R], s3[R], s4[R], s5[R], s6[R];
-  NL_R(t[r] = 0.0; s0[r] = 0.0; s1[r] = 0.0; s2[r] = 0.0; s3[r] = 0.0; s4[r] = 0.0; s5[r] = 0.0; s6[r] = 0.0)
-  int sp = 0, ci = 0;
-  const unsigned long long w0 = e.w[0], w1 = e.w[1], w2 = e.w[2], w3 = e.w[3];
-  double cnext = e.pool[0];
-  for (int i = 0; i < e.n; ++i) {
-    const int j = i >> 3;
-    const unsigned long long w = j == 0 ? w0 : (j == 1 ? w1 : (j == 2 ? w2 : w3));
-    const int op = (int)((w >> (8 * (i & 7))) & 255u);
-    if (op == EXAMG_OP_CONST || op == EXAMG_OP_U) {
-      switch (sp) {                  // push: the old top goes below
-        case 1: NL_R(s0[r] = t[r]) break;
-        case 2: NL_R(s1[r] = t[r]) break;
-        case 3: NL_R(s2[r] = t[r]) break;
-        case 4: NL_R(s3[r] = t[r]) break;
-        case 5: NL_R(s4[r] = t[r]) break;
-        case 6: NL_R(s5[r] = t[r]) break;
-        case 7: NL_R(s6[r] = t[r]) break;
-        default: break;
-      }
-      if (op == EXAMG_OP_CONST) {
-        NL_R(t[r] = cnext)
-        ++ci;
-        cnext = e.pool[ci];
-      } else {
-        NL_R(t[r] = v[r])
-      }
-      ++sp;
-      continue;
-    }
-    if (op == EXAMG_OP_ADD || op == EXAMG_OP_SUB || op == EXAMG_OP_MUL || op == EXAMG_OP_DIV || op == EXAMG_OP_POW || op == EXAMG_OP_MAX ||
-        op == EXAMG_OP_MIN) {
-      double a[R];                   // the value below the top
-      switch (sp) {
-        case 2: NL_R(a[r] = s0[r]) break;
-        case 3: NL_R(a[r] = s1[r]) break;
-        case 4: NL_R(a[r] = s2[r]) break;
-        case 5: NL_R(a[r] = s3[r]) break;
-        case 6: NL_R(a[r] = s4[r]) break;
-        case 7: NL_R(a[r] = s5[r]) break;
-        default: NL_R(a[r] = s6[r]) break;
-      }
-      --sp;
-      switch (op) {
-        case EXAMG_OP_ADD: NL_R(t[r] = a[r] + t[r]) break;
-        case EXAMG_OP_SUB: NL_R(t[r] = a[r] - t[r]) break;
-        case EXAMG_OP_MUL: NL_R(t[r] = a[r] * t[r]) break;
-        case EXAMG_OP_DIV: NL_R(t[r] = a[r] / t[r]) break;
-        case EXAMG_OP_POW: NL_R(t[r] = pow(a[r], t[r])) break;
-        case EXAMG_OP_MAX: NL_R(t[r] = fmax(a[r], t[r])) break;
-        default: NL_R(t[r] = fmin(a[r], t[r])) break;
-      }
-      continue;
-    }
-    switch (op) {
-      case EXAMG_OP_NEG: NL_R(t[r] = -t[r]) break;
-      case EXAMG_OP_SIN: NL_R(t[r] = sin(t[r])) break;
-      case EXAMG_OP_COS: NL_R(t[r] = cos(t[r])) break;
-      case EXAMG_OP_EXP: NL_R(t[r] = exp(t[r])) break;
-      case EXAMG_OP_SINH: NL_R(t[r] = sinh(t[r])) break;
-      case EXAMG_OP_COSH: NL_R(t[r] = cosh(t[r])) break;
-      case EXAMG_OP_SQRT: NL_R(t[r] = sqrt(t[r])) break;
-      case EXAMG_OP_TAN: NL_R(t[r] = tan(t[r])) break;
-      case EXAMG_OP_LOG: NL_R(t[r] = log(t[r])) break;
-      case EXAMG_OP_FABS: NL_R(t[r] = fabs(t[r])) break;
-      default: NL_R(t[r] = tanh(t[r])) break;
-    }
-  }
-  NL_R(res[r] = t[r])
-}
 
 // NENT: the entry count of the stencil when the fold is unrolled (5, 7: coefficients and offsets arrive in two scalar loads and all
 // neighbour loads are in flight together), 0: a loop over a.nent entries.  Same products, same order.

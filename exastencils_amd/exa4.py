@@ -71,9 +71,10 @@ from .exa4_common import (APPLY, RESIDUAL, SMOOTH, _FN_2D_ONLY, _FN_ANY_DIM, _FN
 from .exa4_builtins import Builtins  # noqa: E402
 from .exa4_fusion import LazyFusions  # noqa: E402
 from .exa4_peepholes import Peepholes  # noqa: E402
+from .exa4_conservation import Conservation, _EXPR, expand  # noqa: E402
 
 
-class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonlinear):
+class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonlinear, Conservation):
     """One ExaSlang-4 program bound to a kernel layer (`ops`: HipOps on the GPU), a block decomposition and a
     communicator.  `run()` executes `Function Application`; printed lines are collected in `self.out`."""
 
@@ -193,6 +194,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         self.functions: Dict[str, List[FunctionDecl]] = {}
         for fn in a.functions:
             self.functions.setdefault(fn.name, []).append(fn)
+        self._inline_global_exprs()       # `Expr` macros of the Globals blocks (exa4_conservation.py)
         for name, e in a.globals:
             self.globals[name] = self._eval(e, _Frame(None, {}))
         layouts = {l.name: l for l in a.layouts}
@@ -306,6 +308,12 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             f = Field(fd.name, lvl, lay, self.ops, nslots, None, ())
             if order is not None:
                 f.cell_bc = (BC_NEUMANN, None)
+            elif fd.bc is not None and fd.bc[0] == "call" and fd.bc[1] in self.functions:
+                # a boundary function (`Field hu< global, L, wall_hu@finest ( ) >`): `apply bc` runs it; its ghost loops are faces of
+                # examg_apply_bc_cell (exa4_conservation.py: _recognise_ghost_loop)
+                if fd.bc[3]:
+                    raise Exa4Unsupported("field %s: a boundary function with arguments" % fd.name)
+                f.cell_bc = ("function", fd.bc[1])
             elif fd.bc is not None:
                 f.cell_bc = (BC_DIRICHLET, self._cell_program(fd.bc, lvl))
             else:
@@ -624,6 +632,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                     raise Exa4Unsupported("%s on a non-uniform grid outside a stencil entry or a point expression" % name)
                 h = self.domain.h(self._level_of(e[2], fr))
                 return h[0] * h[1] * h[2] if self.nd == 3 else (h[0] * h[1] if self.nd == 2 else h[0])
+            if _EXPR + name in fr.vars or name in self._global_exprs():      # a scalar `Expr`: evaluated where it is used
+                return self._eval(expand(("id", name, None), dict(self._global_exprs(), **self._expr_defs(fr))), fr)
             m = _COORD.match(name)
             if m:
                 v = fr.vars.get("__" + m.group(2))
@@ -1008,6 +1018,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             return
         if k == "decl":
             fr.vars[s[1]] = self._eval(s[2], fr) if s[2] is not None else 0
+        elif k == "exprdecl":
+            fr.vars[_EXPR + s[1]] = s[3]      # a macro: substituted where it is used (exa4_conservation.py)
         elif k == "assign":
             op, lhs, rhs = s[1], s[2], s[3]
             if lhs[0] != "id":
@@ -1140,7 +1152,11 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         if f.layout.is_cell:
             # a ghost value is a function of the interior: written every time, never assumed valid
             mask = self.domain.face_mask()
-            if f.cell_bc is not None and mask:
+            if f.cell_bc is not None and f.cell_bc[0] == "function":
+                if slot != f.active:
+                    raise Exa4Unsupported("apply bc to a slot of %s other than the active one: its boundary function names the active slot" % f.name)
+                self.call(f.cell_bc[1], f.level)
+            elif f.cell_bc is not None and mask:
                 self.launches += 1
                 self.ops.apply_bc_cell(f.lc, f.data(slot), self.domain.geom(f.level), f.cell_bc[0], f.cell_bc[1], mask)
             return
@@ -1230,6 +1246,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
     def _exec_loop(self, s, fr: _Frame):
         _, target, only, where, reduction, body = s
         f, _ = self._field(target, fr)
+        ghost = self._recognise_ghost_loop(s, f, fr)      # a boundary function's loop over one face (exa4_conservation.py)
+        if ghost is not None:
+            return self._launch(ghost, None, None, None)
         if self._check_cell_body(body, fr) and not f.layout.is_cell:
             raise Exa4Unsupported("loop over node field %s with a body over cell fields" % f.name)
         if f.layout.is_cell and (only is not None or fr.contract is not None):
@@ -1237,6 +1256,11 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         if fr.mcolour is not None:
             return self._exec_loop_multicolour(s, fr)
         boxes, colour = self._loop_boxes(f, only, where, reduction, fr)
+        flux = self._recognise_flux_loop(body, f, only, where, reduction, colour, fr)      # the whole body as ONE explicit update
+        if flux is not None:
+            for b, e in boxes:
+                self._launch(flux, b, e, None)
+            return
         if any(st[0] == "solve" for st in body):
             if len(body) != 1 or reduction is not None or only is not None:
                 raise Exa4Unsupported("solve locally beside other statements, in a reduction or in an `only` loop")
@@ -1328,6 +1352,15 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                             acc = max(acc, self.comm.reduce_value(r, "max"))
                         fr.vars[var] = acc
                         continue
+            k = self._recognise_reduce_expr(op, var, st, locals_, f, fr)      # max | min of a point expression over cell fields
+            if k is not None:
+                tgt = fr.vars if var in fr.vars or var not in self.globals else self.globals
+                acc = tgt[var]
+                for b, e in boxes:
+                    r = self.comm.reduce_value(self._launch(k, b, e, None), op)
+                    acc = max(acc, r) if op == "max" else min(acc, r)
+                tgt[var] = acc
+                continue
             raise Exa4Unsupported("reduction %s over this loop body" % op)
 
     def _exec_stencil_field_init(self, body, boxes, fr: _Frame):

@@ -3,7 +3,9 @@
 line ranges of the constructs covered).
 
 AST: tuples.  Expressions: ("num", v) ("str", s) ("id", name, level) ("fld", name, slot, level) ("sten", name, level)
-("sentry", name, level, offset) ("vfo", name, level, offset) ("call", name, level, args) ("bin", op, a, b) ("neg", a) ("not", a).  Statements: ("decl", ..)
+("sentry", name, level, offset) ("vfo", name, level, offset) ("call", name, level, args) ("bin", op, a, b) ("neg", a) ("not", a)
+("off", expression, offset): an `Expr` name or a field access read at a neighbouring cell (`F@east`, `F@[1, 0]`).  Statements: ("decl", ..)
+("exprdecl", name, levels, expression)
 ("assign", op, lhs, rhs) ("loop", target, only, where, reduction, body) ("comm", phase, what, target) ("applybc", target)
 ("advance", target) ("repeat", n, counter, body) ("until", cond, body) ("if", cond, then, else) ("color", exprs, body)
 ("levelscope", levels, body) ("return", expr) ("callstmt", call) ("repeatwith", conditions, body) ("solve", jacobi, relax, rows of (unknown, lhs, rhs)).  Level specifications: ("single", base, delta) ("all",)
@@ -120,6 +122,9 @@ _MATH = {"sqrt": math.sqrt, "fabs": abs, "abs": abs, "sin": math.sin, "cos": mat
 _COORD = re.compile(r"^vf_(nodePosition|nodePos|boundaryCoord|boundaryPosition|boundaryPos|cellCenter|cellCentre)_([xyz])$")
 _GRIDW = re.compile(r"^vf_(gridWidth|cellWidth)_([xyz])$")
 _CELLVOL = "vf_cellVolume"
+# `X@east` (util/l4/L4_OffsetAlias.scala): the named unit offsets of an access
+_OFFSET_ALIAS = {"center": (0, 0, 0), "east": (1, 0, 0), "west": (-1, 0, 0), "north": (0, 1, 0), "south": (0, -1, 0), "top": (0, 0, 1),
+                 "bottom": (0, 0, -1)}
 
 
 # =====================================================================================================================
@@ -132,6 +137,9 @@ class Parser:
         self.field_names = set(re.findall(r"^\s*Field\s+([A-Za-z_]\w*)", text, re.M))
         self.stencil_names = set(re.findall(r"^\s*Stencil\s+([A-Za-z_]\w*)", text, re.M))
         self.sfield_names = set(re.findall(r"^\s*StencilField\s+([A-Za-z_]\w*)", text, re.M))
+        self.expr_names = set(re.findall(r"^\s*Expr\s+([A-Za-z_]\w*)", text, re.M))
+        self.exprs: List[Tuple[str, object, object]] = []      # `Expr name[@levels] = expression` of the Globals blocks: macros
+        self._ghost_body = False                                # inside `loop over F only ghost [d] on boundary { .. }`
         self.domain = None
         self.layouts: List[LayoutDecl] = []
         self.fields: List[FieldDecl] = []
@@ -346,12 +354,22 @@ class Parser:
         self.expect("Globals")
         self.expect("{")
         while not self.accept("}"):
+            if self.at("Expr"):            # `Expr name[@levels] = expression` (baseExt/l4/L4_ExpressionDeclaration.scala): no type
+                self.exprs.append(self._expr_decl()[1:])
+                continue
             self.next()                    # Var | Val
             name = self.ident()
             self.expect(":")
             self._datatype()
             val = self.expr() if self.accept("=") else ("num", 0.0)
             self.globals.append((name, val))
+
+    def _expr_decl(self):
+        self.expect("Expr")
+        name = self.ident()
+        levels = self.decl_levels()
+        self.expect("=")
+        return ("exprdecl", name, levels, self.expr())
 
     def _datatype(self):
         self.ident()
@@ -455,6 +473,8 @@ class Parser:
                 return ("decl", name, init)
             if w == "loop":
                 return self._loop()
+            if w == "Expr" and self.peek(1).kind == "id":
+                return self._expr_decl()
             if w in ("communicate", "begin", "finish"):
                 phase = "sync"
                 if w != "communicate":
@@ -619,7 +639,13 @@ class Parser:
             self.expect(":")
             reduction = (op, self.ident())
             self.expect(")")
-        return ("loop", target, only, where, reduction, self.block())
+        # the body of a ghost loop on the boundary may read its field at the cell inside (`hu = -hu@[1, 0]`: a boundary function)
+        saved, self._ghost_body = self._ghost_body, only is not None and only[0] == "ghost" and only[2]
+        try:
+            body = self.block()
+        finally:
+            self._ghost_body = saved
+        return ("loop", target, only, where, reduction, body)
 
     # -- expressions ------------------------------------------------------------------------------------------------
     def expr(self, no_rel: bool = False):
@@ -705,15 +731,28 @@ class Parser:
             slot = int(s.text) if s.kind == "num" else s.text
             self.next()
         level = None
-        if self.at("@") and not self.at("[", 1):
+        if self.at("@") and not self.at("[", 1) and self.peek(1).text not in _OFFSET_ALIAS:
             self.next()
             level = self._level_item()
-        if self.at("@") and self.at("[", 1):
+        off = None
+        if self.at("@") and self.peek(1).text in _OFFSET_ALIAS and self.peek(1).kind == "id":
+            # `F1@east`: an `Expr` or a field read at a neighbouring cell; the interpreter adds the offset to every field access inside
+            if name not in self.expr_names and name not in self.field_names:
+                raise Exa4Unsupported("line %d: offset access %s@%s (an Expr or a field is read at a neighbouring cell)" % (t.line, name, self.peek(1).text))
+            self.next()
+            off = _OFFSET_ALIAS[self.next().text]
+        elif self.at("@") and self.at("[", 1):
             if name.startswith("vf_") and name not in self.field_names:
                 # a virtual field of the grid at a neighbouring cell / node: `vf_cellWidth_x@[-1, 0, 0]` (grid/l4/L4_VirtualFieldAccess.scala)
                 self.next()
                 return ("vfo", name, level, tuple(int(_const_value(e)) for e in self._const_list()))
-            raise Exa4Unsupported("line %d: offset access %s@[...]" % (t.line, name))
+            if not (name in self.expr_names or (name in self.field_names and self._ghost_body)):
+                raise Exa4Unsupported("line %d: offset access %s@[...]" % (t.line, name))
+            self.next()
+            off = tuple(int(_const_value(e)) for e in self._const_list())
+            off = off + (0,) * (3 - len(off))
+        if off is not None:
+            return ("off", ("fld", name, slot, level) if name in self.field_names else ("id", name, level), off)
         if name in self.field_names:
             return ("fld", name, slot, level)
         if name in self.stencil_names or name in self.sfield_names:

@@ -21,7 +21,7 @@ from .field import Field, Stencil
 class LoopStmt:
     """What one assignment in a loop body launches.  kind: set | fill_fn | fill_expr | fill_expr_cell | copy | axpby | add_scalar |
     residual | apply | smooth | restrict | restrict_cell | prolong_add | prolong_add_cell | sys_row | pointwise_mul | pointwise_sub |
-    nl_op | nl_smooth | axis_residual | axis_apply | axis_smooth."""
+    nl_op | nl_smooth | axis_residual | axis_apply | axis_smooth | flux_step | reduce_expr | bc_face."""
     kind: str
     D: Field                        # the field assigned to
     ds: int
@@ -246,6 +246,18 @@ class Statements:
         """Issue the loop `k` stands for on the box [b, e): the only kernel-layer calls of loop-body assignments, and their count."""
         ops, kind = self.ops, k.kind
         D, U, F = k.D, k.U, k.F
+        if kind == "bc_face":                 # (exa4_conservation.py) one face of a boundary function; no face: the block has a neighbour there
+            if k.prog[1]:
+                self.launches += 1
+                ops.apply_bc_cell(D.lc, D.data(k.ds), self.domain.geom(D.level), k.prog[0], None, k.prog[1])
+            return None
+        if kind == "reduce_expr":             # the device scalar goes back to the reduction loop, which reads it
+            self.launches += 1
+            return ops.reduce_expr_cell(int(k.s), D.lc, [X.data(s) for X, s in k.prog[0]], k.prog[1], b, e)
+        if kind == "flux_step":
+            ins, outs, spec = k.prog
+            self.launches += 1
+            return ops.flux_step(ins[0][0].lc, [X.data(s) for X, s in ins], D.lc, [X.data(s) for X, s in outs], spec, b, e)
         d = D.data(k.ds)
         u = None if U is None else U.data(k.us)
         lf, f = (None, None) if F is None else (F.lc, F.data(k.fs))

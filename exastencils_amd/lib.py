@@ -125,6 +125,35 @@ class NlExprC(C.Structure):
         return e
 
 
+# ---- explicit flux-form steps on cell fields (include/examg.h: examg_flux_t) ----------------------------------------------------------
+FLUX_MAX_FIELDS, FLUX_MAX_PROGS, FLUX_MAX_COMP, FLUX_MAX_TERMS, FLUX_MAX_ENTRIES = 6, 8, 4, 4, 5
+FLUX_GATHER, FLUX_MARCH = 1, 2            # what examg_flux_route answers (-1 refused, 0 empty box)
+FLUX_DEFAULT = FLUX_MARCH                 # the kernel examg_flux_step takes (the measured table decides it)
+REDUCE_MAX, REDUCE_MIN = 0, 1
+OP_FIELD0 = 32
+# `f<k>` pushes the value of input field k at the cell the program is evaluated at; no `u`, no position
+FLUX_OPS = dict((k, v) for k, v in NL_OPS.items() if k != "u")
+FLUX_OPS.update(("f%d" % k, OP_FIELD0 + k) for k in range(FLUX_MAX_FIELDS))
+
+
+class FluxTermC(C.Structure):
+    """examg_flux_term_t: scale * (P(i + plus) - P(i + minus)), P = prog[prog]."""
+    _fields_ = [("prog", C.c_int32), ("plus", C.c_int32 * 3), ("minus", C.c_int32 * 3), ("scale", C.c_double)]
+
+
+class FluxCompC(C.Structure):
+    """examg_flux_comp_t: one component: a constant axis stencil on in[field] and up to FLUX_MAX_TERMS terms."""
+    _fields_ = [("field", C.c_int32), ("nent", C.c_int32), ("off", (C.c_int32 * 3) * FLUX_MAX_ENTRIES), ("coef", C.c_double * FLUX_MAX_ENTRIES),
+                ("nterms", C.c_int32), ("term", FluxTermC * FLUX_MAX_TERMS)]
+
+
+class FluxC(C.Structure):
+    """examg_flux_t"""
+    _fields_ = [("nfields", C.c_int32), ("nprogs", C.c_int32), ("ncomp", C.c_int32), ("lin", LayoutC), ("lout", LayoutC),
+                ("in_", C.c_void_p * FLUX_MAX_FIELDS), ("out", C.c_void_p * FLUX_MAX_COMP), ("prog", NlExprC * FLUX_MAX_PROGS),
+                ("comp", FluxCompC * FLUX_MAX_COMP)]
+
+
 class ExamgError(RuntimeError):
     pass
 
@@ -153,13 +182,14 @@ SYMBOLS = [
     "examg_nl_op", "examg_nl_smooth",
     "examg_gs_sweep", "examg_gs_route",
     "examg_axis_op", "examg_axis_route", "examg_fill_expr_grid", "examg_apply_dirichlet_expr_grid", "examg_max_err_expr_grid",
+    "examg_flux_step", "examg_flux_route", "examg_reduce_expr_cell",
 ]
 
 COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 128
 EXCH_DUP, EXCH_GHOST, EXCH_ALL, EXCH_CONCURRENT_AXES = 1, 2, 3, 4
 PASS_TMP_PLANES_VALID = 8
-BC_DIRICHLET, BC_NEUMANN = 0, 1
+BC_DIRICHLET, BC_NEUMANN, BC_NEGATE = 0, 1, 2
 CG_ALPHA_FROM_NORM, CG_NO_BC, CG_ZERO_START = 1, 2, 4
 GS_REFUSED, GS_EMPTY, GS_ONE_WORKGROUP, GS_TILED, GS_PER_HYPERPLANE = -1, 0, 1, 2, 3      # examg_gs_route
 
@@ -292,6 +322,10 @@ def load(path=None):
     L.examg_fill_expr_grid.argtypes = [lp, vp, rp, ep, ip, ip, vp]
     L.examg_apply_dirichlet_expr_grid.argtypes = [lp, vp, rp, ep, C.c_uint32, vp]
     L.examg_max_err_expr_grid.argtypes = [lp, vp, rp, ep, ip, ip, vp, vp, vp]
+    xp = C.POINTER(FluxC)
+    L.examg_flux_step.argtypes = [xp, ip, ip, vp]
+    L.examg_flux_route.argtypes = [xp, ip, ip]
+    L.examg_reduce_expr_cell.argtypes = [C.c_int, C.c_int, lp, C.POINTER(vp), np_, ip, ip, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("examg_version", "examg_last_error", "examg_device_count", "examg_reduce_work_bytes", "examg_exchange_workspace_bytes",
@@ -309,6 +343,9 @@ def load(path=None):
     if hasattr(L, "examg_debug_nl_gather_only"):     # debug build only: star stencils of the semilinear kernels on the gather kernel
         L.examg_debug_nl_gather_only.argtypes = [C.c_int]
         L.examg_debug_nl_gather_only.restype = C.c_int
+    if hasattr(L, "examg_debug_flux_route"):         # debug build only: examg_flux_step on the kernel named (0: the default)
+        L.examg_debug_flux_route.argtypes = [C.c_int]
+        L.examg_debug_flux_route.restype = C.c_int
     if hasattr(L, "examg_debug_sys_narrow"):         # debug build only: the 8-byte form of the system kernels
         L.examg_debug_sys_narrow.argtypes = [C.c_int]
         L.examg_debug_sys_narrow.restype = C.c_int

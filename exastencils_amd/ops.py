@@ -307,7 +307,8 @@ class HipOps:
         return out
 
     def apply_bc_cell(self, l, x, geom, kind: int, expr, face_mask: int):
-        """kind: lib.BC_DIRICHLET (expr: the boundary value at the face centres) or lib.BC_NEUMANN (expr may be None)."""
+        """kind: lib.BC_DIRICHLET (expr: the boundary value at the face centres), lib.BC_NEUMANN (ghost = interior) or lib.BC_NEGATE
+        (ghost = -interior: a reflecting wall); expr may be None for the last two."""
         check(self.L.examg_apply_bc_cell(C.byref(l), self.ptr(x), C.byref(geom), int(kind), C.byref(expr) if expr is not None else None,
                                          int(face_mask), self._stream()), "examg_apply_bc_cell")
 
@@ -365,6 +366,27 @@ class HipOps:
         sc = st.c_struct(self.ptr)
         check(self.L.examg_nl_smooth(C.byref(lu), self.ptr(u_in), C.byref(ld), self.ptr(u_out), C.byref(lf), self.ptr(rhs), C.byref(sc),
                                      C.byref(c), C.byref(d), float(w), int(colour), ivec(begin), ivec(end), self._stream()), "examg_nl_smooth")
+
+    # -- explicit flux-form steps on cell fields -------------------------------------------------------
+    def flux_step(self, lin, ins, lout, outs, spec, begin, end):
+        """One explicit update of the components of `spec` (flux.FluxSpec): outs[c] = C_c * ins[field_c] + sum_t scale_t * (P_t(i + plus_t) -
+        P_t(i + minus_t)), one launch for all components (examg_flux_step)."""
+        fx = spec.c_struct(self.ptr, lin, ins, lout, outs)
+        check(self.L.examg_flux_step(C.byref(fx), ivec(begin), ivec(end), self._stream()), "examg_flux_step")
+
+    def flux_route(self, lin, ins, lout, outs, spec, begin, end) -> int:
+        """What flux_step does with these arguments: -1 refused (the reason in examg_last_error), 0 empty box, lib.FLUX_GATHER, lib.FLUX_MARCH."""
+        fx = spec.c_struct(self.ptr, lin, ins, lout, outs)
+        return int(self.L.examg_flux_route(C.byref(fx), ivec(begin), ivec(end)))
+
+    def reduce_expr_cell(self, op: int, l, xs, prog, begin, end, out=None):
+        """max (lib.REDUCE_MAX) or min (lib.REDUCE_MIN) over the box of the program over the cell fields xs at the cell; prog: lib.NlExprC
+        over lib.FLUX_OPS (flux.field_program).  The result stays on the device (examg_reduce_expr_cell)."""
+        out = self.new_scalar() if out is None else out
+        ptrs = (C.c_void_p * len(xs))(*[self.ptr(x) for x in xs])
+        check(self.L.examg_reduce_expr_cell(int(op), len(xs), C.byref(l), ptrs, C.byref(prog), ivec(begin), ivec(end), self.ptr(out),
+                                            self.ptr(self._work), self._stream()), "examg_reduce_expr_cell")
+        return out
 
     def scalar_value(self, t) -> float:
         """Host value of a device scalar (the reference's 8-byte D2H copy after a reduction)."""

@@ -689,6 +689,8 @@ int examg_max_err_expr_cell(const examg_layout_t *l, const double *x, const exam
  * face in face_mask (bit 2*d + (side > 0)), all faces in ONE launch, order 1:
  *   EXAMG_BC_DIRICHLET: ghost = 2.0 * g(face centre) - interior   (boundary/ir/IR_DirichletBC.scala, generateFieldUpdatesCell)
  *   EXAMG_BC_NEUMANN  : ghost = interior                           (boundary/ir/IR_NeumannBC.scala, generateFieldUpdatesCell)
+ *   EXAMG_BC_NEGATE   : ghost = -interior                          (a reflecting wall written as a boundary function:
+ *                                                                   `loop over hu only ghost [-1, 0] on boundary { hu = -hu@[1, 0] }`)
  * g is the program `expr` (a constant is a one-instruction program; ignored for Neumann) evaluated at the face centre
  * (boundary/ir/IR_HandleBoundaries.scala:55-70): the cell centre in the tangential dimensions, the node position of the face
  * (index 0 below, index inner above) in the normal one.
@@ -696,7 +698,7 @@ int examg_max_err_expr_cell(const examg_layout_t *l, const double *x, const exam
  * faces one after the other over a range that includes them; a cell stencil with entries off the axes would see the
  * difference, which is why the interpreter refuses those (only axis entries read ghosts, and every axis ghost is written
  * here exactly as the reference writes it).  Needs ghost >= 1 in every dimension of the mask. */
-enum { EXAMG_BC_DIRICHLET = 0, EXAMG_BC_NEUMANN = 1 };
+enum { EXAMG_BC_DIRICHLET = 0, EXAMG_BC_NEUMANN = 1, EXAMG_BC_NEGATE = 2 };
 int examg_apply_bc_cell(const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
                         uint32_t face_mask, examg_stream_t stream);
 
@@ -912,6 +914,85 @@ int examg_axis_op(int mode, const examg_layout_t *lu, const double *u, const exa
                   examg_stream_t stream);
 int examg_axis_route(int mode, const examg_layout_t *lu, const examg_layout_t *lf, const examg_layout_t *ld, const examg_axis_stencil_t *st,
                      int colour, const int32_t *begin, const int32_t *end);
+
+/* ---- Explicit flux-form time steps on cell fields ---------------------------------------------------------------------------
+ * An explicit finite-volume update of coupled cell fields in 2-D: every component is a constant axis stencil on one field plus scaled
+ * differences of point expressions evaluated at two neighbouring cells -- the Lax-Friedrichs step of the shallow-water equations
+ * (Examples/SWE/2D_FV_SWE.exa4: `hNext = Centering * h - (dt / dx) * 0.5 * ( F0@east - F0@west ) - ..`).
+ *
+ * examg_flux_t:
+ *   nfields, in[k]    1 .. EXAMG_FLUX_MAX_FIELDS input cell fields, all in the layout lin (ghost >= 1 in x and y where the box touches them)
+ *   nprogs, prog[p]   0 .. EXAMG_FLUX_MAX_PROGS point programs in the compact type of the semilinear kernels.  EXAMG_OP_FIELD0 + k pushes the
+ *                     value of in[k] AT THE CELL THE PROGRAM IS EVALUATED AT (k < nfields).  EXAMG_OP_U and the position and cell-width
+ *                     opcodes are refused here; EXAMG_OP_FIELD* is refused by every other entry point.  Limits as for examg_nlexpr_t:
+ *                     EXAMG_MAX_NL_EXPR (32) instructions, an operand stack of EXAMG_NL_STACK (8).
+ *   ncomp, comp[c]    1 .. EXAMG_FLUX_MAX_COMP components:
+ *       field         the index in `in` of the field q the stencil multiplies
+ *       nent, off, coef   the constant stencil C_c: 1 .. EXAMG_FLUX_MAX_ENTRIES entries, each the centre or a unit axis offset in x or y
+ *       nterms, term[t]   0 .. EXAMG_FLUX_MAX_TERMS terms {prog, plus, minus, scale}; plus and minus are each the zero offset or a unit
+ *                         axis offset in x or y
+ *   out[c]            the destination of component c, in the layout lout; overlaps no input and no other destination
+ *
+ * Arithmetic per cell i of [begin, end), fp64, no contraction:
+ *   acc = C_c[0] * q(i + o_0);  acc = acc + C_c[k] * q(i + o_k)                      entries in declared order
+ *   acc = acc + scale_t * ( P_t(i + plus_t) - P_t(i + minus_t) )                     terms in declared order
+ *   out_c(i) = acc
+ * P_t(j) is the program prog[term.prog] evaluated in the order of the program over the values in[k](j) at that ONE cell j.
+ * Only the box of each out[c] is written.  Reads the inputs on the box and its one-cell axis shell.
+ *
+ * Refused before anything is launched, each with its own text in examg_last_error: layouts that are not 2-D (the 3-D kernels are not
+ * built); a layout with duplicate layers (a node layout) or under a layout transformation; nfields, nprogs, ncomp, nent (an empty C_c
+ * too) or nterms outside the limits; a field or program index out of range; an offset of a term or a stencil entry off the axes, of
+ * reach 2 or in z; an out[c] that overlaps an input or another out; a box that leaves lout, or that grown by one cell leaves lin; a
+ * program that is empty, too long, too deep, breaks the stack discipline or holds a refused opcode.  An empty box is a no-op that
+ * returns 0.  Nothing is allocated; the launch is capturable.
+ *
+ * Two kernels, the same bits.  EXAMG_FLUX_GATHER: one lane per cell, x fastest; every term evaluates its program at both of its
+ * cells; it takes any admissible call.  EXAMG_FLUX_MARCH: every program is evaluated once per cell -- a wave owns a window of 64
+ * columns (62 of them written, the two halo columns are recomputed by the neighbouring windows) and marches in y two rows at a time with
+ * the program values and field values of the rows y - 1 .. y + 2 in registers; x neighbours come from the adjacent lanes.  It takes
+ * any admissible call too.  examg_flux_route answers which kernel examg_flux_step runs with these arguments, nothing launched: -1
+ * refused (error text set), 0 empty box, EXAMG_FLUX_GATHER or EXAMG_FLUX_MARCH. */
+#define EXAMG_OP_FIELD0 32
+#define EXAMG_FLUX_MAX_FIELDS 6
+#define EXAMG_FLUX_MAX_PROGS 8
+#define EXAMG_FLUX_MAX_COMP 4
+#define EXAMG_FLUX_MAX_TERMS 4
+#define EXAMG_FLUX_MAX_ENTRIES 5
+enum { EXAMG_FLUX_GATHER = 1, EXAMG_FLUX_MARCH = 2 };
+typedef struct examg_flux_term {
+  int32_t prog;
+  int32_t plus[3];
+  int32_t minus[3];
+  double scale;
+} examg_flux_term_t;
+typedef struct examg_flux_comp {
+  int32_t field;
+  int32_t nent;
+  int32_t off[EXAMG_FLUX_MAX_ENTRIES][3];
+  double coef[EXAMG_FLUX_MAX_ENTRIES];
+  int32_t nterms;
+  examg_flux_term_t term[EXAMG_FLUX_MAX_TERMS];
+} examg_flux_comp_t;
+typedef struct examg_flux {
+  int32_t nfields, nprogs, ncomp;
+  examg_layout_t lin, lout;
+  const double *in[EXAMG_FLUX_MAX_FIELDS];
+  double *out[EXAMG_FLUX_MAX_COMP];
+  examg_nlexpr_t prog[EXAMG_FLUX_MAX_PROGS];
+  examg_flux_comp_t comp[EXAMG_FLUX_MAX_COMP];
+} examg_flux_t;
+int examg_flux_step(const examg_flux_t *fx, const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_flux_route(const examg_flux_t *fx, const int32_t *begin, const int32_t *end);
+
+/* max (EXAMG_REDUCE_MAX) or min (EXAMG_REDUCE_MIN) over the cells of [begin, end) of one such program over the values x[k] (k < nfields <=
+ * EXAMG_FLUX_MAX_FIELDS, all in the layout l) at the cell: `loop over h with reduction ( max : v ) { v = max ( v, fabs ( hu / h ) + sqrt ( g * h ) ) }`.
+ * The result stays on the device (*result; work: examg_reduce_work_bytes() bytes), in two stages like every reduction here; fmax and
+ * fmin are exact, so the result has the same bits in any order of evaluation.  An empty box gives the identity: -inf for max, +inf for
+ * min.  Refusals as for examg_flux_step: layouts (2-D or 3-D here), the program, a box that leaves the allocation, an unknown op. */
+enum { EXAMG_REDUCE_MAX = 0, EXAMG_REDUCE_MIN = 1 };
+int examg_reduce_expr_cell(int op, int nfields, const examg_layout_t *l, const double *const *x, const examg_nlexpr_t *prog, const int32_t *begin,
+                           const int32_t *end, double *result, void *work, examg_stream_t stream);
 
 #ifdef __cplusplus
 }

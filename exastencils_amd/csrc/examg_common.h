@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <cmath>
 #include <type_traits>
 
 #include "../../include/examg.h"
@@ -208,11 +209,21 @@ struct Coef7 {
 // (Compiler/src/exastencils/stencil/ir/IR_StencilConvolution.scala:65-68).
 // ORDER 0: entries c,-x,+x,-y,+y,-z,+z (Benchmark/Poisson3D/3D_FD_Poisson_fromL4.exa4:39-47)
 // ORDER 1: entries c,+x,-x,+y,-y,+z,-z (Testing/Smoothers/Jac.exa4:55-63)
-template <int ORDER>
+// FMA: entries 1..6 as fused multiply-adds, for launches whose six off-centre coefficients are +-2^e, e >= 0 (pow2_offdiag7): such a
+// product is exact for every double that it does not overflow, so acc + c*x and fma(c, x, acc) round the same real number once -- the
+// same bits (the build keeps -ffp-contract=off: the fusion is this explicit one only).
+template <int ORDER, bool FMA = false>
 __device__ __forceinline__ double conv7(const Coef7 &k, double c, double xm, double xp, double ym, double yp, double zm,
                                         double zp) {
   double acc = k.c[0] * c;
-  if (ORDER == 0) {
+  if (FMA) {
+    acc = __builtin_fma(k.c[1], ORDER == 0 ? xm : xp, acc);
+    acc = __builtin_fma(k.c[2], ORDER == 0 ? xp : xm, acc);
+    acc = __builtin_fma(k.c[3], ORDER == 0 ? ym : yp, acc);
+    acc = __builtin_fma(k.c[4], ORDER == 0 ? yp : ym, acc);
+    acc = __builtin_fma(k.c[5], ORDER == 0 ? zm : zp, acc);
+    acc = __builtin_fma(k.c[6], ORDER == 0 ? zp : zm, acc);
+  } else if (ORDER == 0) {
     acc = acc + k.c[1] * xm;
     acc = acc + k.c[2] * xp;
     acc = acc + k.c[3] * ym;
@@ -244,6 +255,18 @@ static inline int star7_order(const examg_stencil_t *st) {
   return m0 ? 0 : (m1 ? 1 : -1);
 }
 static inline int canonical_order7(const examg_stencil_t *st) { return st->cfield ? -1 : star7_order(st); }   // ... and a constant stencil
+
+// ... whose six off-centre coefficients are all +-2^e with e >= 0 (finite, not zero: frexp mantissa +-0.5, exponent >= 1)?  Then conv7<.., FMA>
+// gives conv7's bits.  All six or none: one kernel template flag.  (1/h^2 of every power-of-two grid, laplace_unit's -1.0)
+static inline bool pow2_offdiag7(const examg_stencil_t *st) {
+  if (canonical_order7(st) < 0) return false;
+  for (int k = 1; k < 7; ++k) {
+    const double c = st->coef[k];
+    int e = 0;
+    if (!std::isfinite(c) || c == 0.0 || std::fabs(std::frexp(c, &e)) != 0.5 || e < 1) return false;
+  }
+  return true;
+}
 
 // 27-entry stencil field, the centre entry first and the diagonal (the unrolled kernels read both from entry 0); callers add their own conditions
 static inline bool stencil_field27(const examg_stencil_t *st) {

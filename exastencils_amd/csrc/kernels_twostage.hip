@@ -67,7 +67,7 @@ struct TSProl {
 //
 // VAR: 0 = as described; 1 = PROL; 2 = the input field is zero everywhere (a coarse level's first pre-smoothing pass after
 // `Solution = 0`): nothing is loaded for it, the arithmetic is the same expression on the constant 0.0.
-template <int ORDER, bool COL, int NW, bool NT, int WPE, int VAR, int PF = 0, int RPW = 2>
+template <int ORDER, bool COL, int NW, bool NT, int WPE, int VAR, int PF = 0, int RPW = 2, bool FMA = false>
 __global__ void __launch_bounds__(64 * NW, WPE)
 k_two_stage7_lds(LayoutDev lu, const double *__restrict__ u, LayoutDev lf, const double *__restrict__ rhs,
                  double *__restrict__ out, Coef7 k, double w, Box box, TSGeom g, TSProl pr) {
@@ -361,21 +361,21 @@ k_two_stage7_lds(LayoutDev lu, const double *__restrict__ u, LayoutDev lf, const
       if (COL) {
         if constexpr (((r + PH) & 1) == PFW) {
           const double xl = lane_below0(c.y);
-          const double acc = conv7<ORDER>(k, c.x, xl, c.y, ym.x, yp.x, Um[r].x, Up[r].x);
+          const double acc = conv7<ORDER, FMA>(k, c.x, xl, c.y, ym.x, yp.x, Um[r].x, Up[r].x);
           const double nv = c.x + w * (f.x - acc);
           Vn[r].x = (in1_a && on) ? nv : c.x;
           Vn[r].y = c.y;
         } else {
           const double xr = lane_above0(c.x);
-          const double acc = conv7<ORDER>(k, c.y, c.x, xr, ym.y, yp.y, Um[r].y, Up[r].y);
+          const double acc = conv7<ORDER, FMA>(k, c.y, c.x, xr, ym.y, yp.y, Um[r].y, Up[r].y);
           const double nv = c.y + w * (f.y - acc);
           Vn[r].x = c.x;
           Vn[r].y = (in1_b && on) ? nv : c.y;
         }
       } else {
         const double xl = lane_below0(c.y), xr = lane_above0(c.x);
-        const double acc_a = conv7<ORDER>(k, c.x, xl, c.y, ym.x, yp.x, Um[r].x, Up[r].x);
-        const double acc_b = conv7<ORDER>(k, c.y, c.x, xr, ym.y, yp.y, Um[r].y, Up[r].y);
+        const double acc_a = conv7<ORDER, FMA>(k, c.x, xl, c.y, ym.x, yp.x, Um[r].x, Up[r].x);
+        const double acc_b = conv7<ORDER, FMA>(k, c.y, c.x, xr, ym.y, yp.y, Um[r].y, Up[r].y);
         const double na = c.x + w * (f.x - acc_a);
         const double nb = c.y + w * (f.y - acc_b);
         Vn[r].x = (in1_a && on) ? na : c.x;
@@ -396,17 +396,17 @@ k_two_stage7_lds(LayoutDev lu, const double *__restrict__ u, LayoutDev lf, const
         if (COL) {
           if constexpr (((r + PH) & 1) == PFW) {
             const double xl = lane_below0(c.y);
-            const double acc = conv7<ORDER>(k, c.x, xl, c.y, ym.x, yp.x, Vm[r].x, Vn[r].x);
+            const double acc = conv7<ORDER, FMA>(k, c.x, xl, c.y, ym.x, yp.x, Vm[r].x, Vn[r].x);
             o.x = c.x + w * (Fm[r].x - acc);      // no select: a lane outside the box does not store
           } else {
             const double xr = lane_above0(c.x);
-            const double acc = conv7<ORDER>(k, c.y, c.x, xr, ym.y, yp.y, Vm[r].y, Vn[r].y);
+            const double acc = conv7<ORDER, FMA>(k, c.y, c.x, xr, ym.y, yp.y, Vm[r].y, Vn[r].y);
             o.y = c.y + w * (Fm[r].y - acc);
           }
         } else {
           const double xl = lane_below0(c.y), xr = lane_above0(c.x);
-          const double acc_a = conv7<ORDER>(k, c.x, xl, c.y, ym.x, yp.x, Vm[r].x, Vn[r].x);
-          const double acc_b = conv7<ORDER>(k, c.y, c.x, xr, ym.y, yp.y, Vm[r].y, Vn[r].y);
+          const double acc_a = conv7<ORDER, FMA>(k, c.x, xl, c.y, ym.x, yp.x, Vm[r].x, Vn[r].x);
+          const double acc_b = conv7<ORDER, FMA>(k, c.y, c.x, xr, ym.y, yp.y, Vm[r].y, Vn[r].y);
           o.x = c.x + w * (Fm[r].x - acc_a);
           o.y = c.y + w * (Fm[r].y - acc_b);
         }
@@ -528,6 +528,7 @@ static thread_local int g_ts_lds = -2;
 static thread_local int g_ts_nt = -1;          // stores of the plain passes: -1 by size, 1 non-temporal, 0 plain (examg_debug_two_stage_nt)
 static thread_local int g_ts_wpe = 1;          // plain passes: 4 = capped at 128 VGPRs (examg_debug_two_stage_prol(wpe + 10) sets it)
 static thread_local int g_ts_prol_wpe = 1;     // PROL variants: 1 = uncapped (151 / 176 VGPRs: 512^3 0.742 ms), 4 = capped at 128 VGPRs (spills in the unrolled loop: 1.15 ms)
+static thread_local int g_pow2_fma_off = 0;    // examg_debug_pow2_fma(0): the separate products and sums on every launch (A/B, parity tests)
 
 template <bool COL, int NW, int WPE = 1, int RPW = 2>
 static int launch_two_stage_lds(const examg_layout_t *lu_, const double *u, const examg_layout_t *lf_, const double *rhs,
@@ -625,11 +626,22 @@ static int launch_two_stage_lds(const examg_layout_t *lu_, const double *u, cons
   // what this one wrote (tools/ab_nt.py, ping-pong passes, non-temporal / plain, ms: 128^3 0.0158 / 0.0142, 192^3 0.0433 / 0.0339,
   // 256^3 0.0888 / 0.1086, 384^3 0.305 / 0.333, 512^3 0.652 / 0.708).  Plain passes only.
   const bool nt = g_ts_nt >= 0 ? g_ts_nt != 0 : box.count() * 24LL > 200000000LL;
+  // The plain Jacobi pair of eight waves with streaming stores (two and three rows per wave: the pair from 192 rows and 8.4 * 10^6 points
+  // on) has the form with the six off-centre products fused into the sums (conv7<.., FMA>; launch_three_stage_shape) -- no scratch, same
+  // occupancy, tools/ab_libs.py 512^3 0.6433 -> 0.6359 ms, 256^3 0.0907 -> 0.0890.  The red-black sweep of the same shape gains nothing by
+  // it (0.6360 -> 0.6361, 0.0889 -> 0.0886) and keeps its separate products, as do the forms that were not measured.
+  constexpr bool TS_FMA_FORM = !COL && NW == 8;
+  const bool fma = TS_FMA_FORM && !g_pow2_fma_off && pow2_offdiag7(st);
 #define EXAMG_TS_LAUNCH(ORD, W, V, PFV)                                                                                                               \
   do {                                                                                                                                                \
     if ((V) == 0 && (W) == 1 && !nt)                                                                                                                  \
       hipLaunchKernelGGL((k_two_stage7_lds<ORD, COL, NW, false, 1, 0, PFV, RPW>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g, pr);           \
-    else                                                                                                                                              \
+    else if constexpr (TS_FMA_FORM && (V) == 0 && (W) == 1) {                                                                                         \
+      if (fma)                                                                                                                                        \
+        hipLaunchKernelGGL((k_two_stage7_lds<ORD, COL, NW, true, 1, 0, PFV, RPW, true>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g, pr);   \
+      else                                                                                                                                            \
+        hipLaunchKernelGGL((k_two_stage7_lds<ORD, COL, NW, true, 1, 0, PFV, RPW>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g, pr);         \
+    } else                                                                                                                                            \
       hipLaunchKernelGGL((k_two_stage7_lds<ORD, COL, NW, true, W, V, PFV, ((V) == 0 ? RPW : 2)>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g, pr); \
   } while (0)
 #define EXAMG_TS_LAUNCH_PF(ORD, W, V)              \
@@ -734,7 +746,7 @@ constexpr int TS3_OUT = 120;   // outputs per 128-point window: lanes 2 .. 61
 // colour g.first again (three sweeps = six colour loops = two such passes, the second one starting with the other colour).  Which point of a
 // pair a stage updates is the same for all three stages of a step (plane and colour both move by one from stage to stage) and wave-uniform
 // per row: one convolution per pair and stage, the other point passes through.
-template <int ORDER, int NW, bool NT, int RPW = 3, bool COL = false>
+template <int ORDER, int NW, bool NT, int RPW = 3, bool COL = false, bool FMA = false>
 __global__ void __launch_bounds__(64 * NW, 1)
 k_three_stage7_lds(LayoutDev lu, const double *__restrict__ u, LayoutDev lf, const double *__restrict__ rhs,
                    double *__restrict__ out, Coef7 k, double w, Box box, TSGeom g) {
@@ -873,8 +885,8 @@ k_three_stage7_lds(LayoutDev lu, const double *__restrict__ u, LayoutDev lf, con
   // one Jacobi update of a pair: centre c, y neighbours ym / yp, z neighbours zm / zp, right-hand side f
   auto jac = [&](d2 c, d2 ym, d2 yp, d2 zm, d2 zp, d2 f) {
     const double xl = lane_below0(c.y), xr = lane_above0(c.x);
-    const double acc_a = conv7<ORDER>(k, c.x, xl, c.y, ym.x, yp.x, zm.x, zp.x);
-    const double acc_b = conv7<ORDER>(k, c.y, c.x, xr, ym.y, yp.y, zm.y, zp.y);
+    const double acc_a = conv7<ORDER, FMA>(k, c.x, xl, c.y, ym.x, yp.x, zm.x, zp.x);
+    const double acc_b = conv7<ORDER, FMA>(k, c.y, c.x, xr, ym.y, yp.y, zm.y, zp.y);
     d2 n;
     n.x = c.x + w * (f.x - acc_a);
     n.y = c.y + w * (f.y - acc_b);
@@ -882,12 +894,12 @@ k_three_stage7_lds(LayoutDev lu, const double *__restrict__ u, LayoutDev lf, con
   };
   auto jac_x = [&](d2 c, d2 ym, d2 yp, d2 zm, d2 zp, d2 f) {      // the first point of the pair only
     const double xl = lane_below0(c.y);
-    const double acc = conv7<ORDER>(k, c.x, xl, c.y, ym.x, yp.x, zm.x, zp.x);
+    const double acc = conv7<ORDER, FMA>(k, c.x, xl, c.y, ym.x, yp.x, zm.x, zp.x);
     return c.x + w * (f.x - acc);
   };
   auto jac_y = [&](d2 c, d2 ym, d2 yp, d2 zm, d2 zp, d2 f) {      // the second point only
     const double xr = lane_above0(c.x);
-    const double acc = conv7<ORDER>(k, c.y, c.x, xr, ym.y, yp.y, zm.y, zp.y);
+    const double acc = conv7<ORDER, FMA>(k, c.y, c.x, xr, ym.y, yp.y, zm.y, zp.y);
     return c.y + w * (f.y - acc);
   };
   // COL: the update of a pair in the step of plane q, row r -- the first point if its colour (x + y + z) & 1 is the colour of the stage
@@ -1039,12 +1051,22 @@ static int launch_three_stage_shape(const examg_layout_t *lu_, const double *u, 
   // rounds of 256 workgroups x (planes per chunk + 8), chunks of 16 .. 64 planes where the box has them.  tools/time_three_stage.py --dbg,
   // MI355X, ms per pass at 512^3, 16 / 24 / 40 / 48 / 56 / 64 / 128 planes: 0.887 / 0.834 / 0.825 / 0.834 / 0.815 / 0.899 / 1.023 (another box:
   // 0.861 / 0.810 / - / 0.801 / - / 0.867 / -); 256^3, 16 / 20 / 44 / 64: 0.154 / 0.129 / 0.130 / 0.173
+  // The fused form (fma below) from 10^8 points on: chunks of at most 28 planes.  Its plane step issues a quarter fewer instructions, and
+  // the steps a chunk spends on its halo planes cost little else.  Same tool, two boxes, 512^3, rule (48) / 20 / 24 / 28 / 40 / 56 planes:
+  // 0.690 / 0.670 / 0.666 / 0.672 / 0.682 / 0.686 and 0.666 / 0.652 / 0.643 / 0.647 / 0.653 / 0.662 ms (the separate products in the same
+  // session: 0.681 / 0.706 / 0.689 / 0.690 / 0.676 / 0.671 -- they keep the long chunks); 1024^3 fused, 20 / 24 / 28 / 36 / 48 / 64 (the rule
+  // above) planes: 5.598 / 5.591 / 5.575 / 5.593 / 5.610 / 5.659.  Below 10^8 points the rule above stands for both forms (256^3 fused: rule
+  // (44) 0.0967, 20: 0.0957, 24: 0.106, 28: 0.118).
+  // off-centre coefficients +-2^e (every power-of-two grid): the six products of a convolution fused into the sums, same bits (conv7), 10
+  // instead of 16 fp64 instructions per update.  The Jacobi form only: the colour form spills 28 bytes with them (0.71 -> 0.83 ms at 512^3).
+  const bool fma = !COL && !g_pow2_fma_off && pow2_offdiag7(st);
+  const int cmax = (fma && box.count() >= 100000000LL) ? 28 : 64;
   int zc = n2;
   {
     long long best = -1;
     for (int t = 1; t <= (n2 + 7) / 8; ++t) {
       const int c = (n2 + t - 1) / t, tt = (n2 + c - 1) / c;
-      if ((c > 64 && t < (n2 + 7) / 8) || (c < 16 && t > 1)) continue;
+      if ((c > cmax && t < (n2 + 7) / 8) || (c < 16 && t > 1)) continue;
       const long long cost = (((long long)xy * tt + 255) / 256) * (((c + 4 + 3) & ~3) + 4);      // whole groups of four steps
       if (best < 0 || cost < best) { best = cost; zc = c; }
     }
@@ -1067,8 +1089,13 @@ static int launch_three_stage_shape(const examg_layout_t *lu_, const double *u, 
   dim3 block(64, NW, 1), grid(g.nblocks, 1, 1);
   with_order(ord, [&](auto O) {
     constexpr int ORD = decltype(O)::value;
-    if (nt) hipLaunchKernelGGL((k_three_stage7_lds<ORD, NW, true, RPW, COL>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g);
-    else hipLaunchKernelGGL((k_three_stage7_lds<ORD, NW, false, RPW, COL>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g);
+    auto go = [&](auto NTc, auto Fc) {
+      hipLaunchKernelGGL((k_three_stage7_lds<ORD, NW, decltype(NTc)::value, RPW, COL, decltype(Fc)::value>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g);
+    };
+    if constexpr (!COL) {
+      if (fma) return nt ? go(std::true_type{}, std::true_type{}) : go(std::false_type{}, std::true_type{});
+    }
+    return nt ? go(std::true_type{}, std::false_type{}) : go(std::false_type{}, std::false_type{});
   });
   EXAMG_CHECK_LAUNCH("k_three_stage7_lds");
   return 0;
@@ -1111,6 +1138,11 @@ extern "C" int examg_debug_three_stage(int disable, int zc) {
   g_ts3_disable = disable == 1;
   g_ts3_minpts = disable == 2 ? (1LL << 20) : 8000000LL;
   g_ts3_zc = zc > 0 ? zc : -1;
+  return 0;
+}
+
+extern "C" int examg_debug_pow2_fma(int on) {
+  g_pow2_fma_off = on ? 0 : 1;
   return 0;
 }
 
@@ -1362,6 +1394,10 @@ extern "C" int examg_three_stage_eligible(const examg_layout_t *lu, const examg_
   if (!lu || !lf || !st || !begin || !end) return 0;
   return three_stage_ok(lu, lf, st, make_box(begin, end)) ? 1 : 0;
 }
+
+// 1 if the one-pass kernels that have the form fuse the six off-centre products of this stencil into their sums (conv7<.., FMA>): a constant
+// 7-point star in a canonical order whose off-centre coefficients are all +-2^e, e >= 0.  The three-step Jacobi pass and the eight-wave Jacobi pair.
+extern "C" int examg_pow2_fma_eligible(const examg_stencil_t *st) { return st && pow2_offdiag7(st) ? 1 : 0; }
 
 // Three colour loops of a red-black smoother in ONE pass, out of place: colour `first` on [begin,end), then the other colour, then `first`
 // again (`repeat 3 times { color with { (i0 + i1 + i2) % 2 ... } }`, Benchmark/Poisson3D/3D_FD_Poisson_fromL4.exa4:204-213, is six colour

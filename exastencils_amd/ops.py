@@ -169,6 +169,11 @@ class HipOps:
         sc = st.c_struct(self.ptr)
         return bool(self.L.examg_three_stage_eligible(C.byref(lu), C.byref(lf), C.byref(sc), ivec(begin), ivec(end)))
 
+    def pow2_fma_eligible(self, st: Stencil) -> bool:
+        """Are the six off-centre coefficients +-2^e, e >= 0, so that the three-step Jacobi pass fuses their products into the sums?"""
+        sc = st.c_struct(self.ptr)
+        return bool(self.L.examg_pow2_fma_eligible(C.byref(sc)))
+
     def jacobi_residual(self, lu, u_in, u_out, lf, rhs, lr, res, st: Stencil, w: float, begin, end):
         """One Jacobi step and the residual of its result in one pass (examg_jacobi_residual)."""
         sc = st.c_struct(self.ptr)

@@ -262,6 +262,14 @@ int examg_rbgs_colours3(const examg_layout_t *lu, const double *u_in, double *u_
 int examg_three_stage_eligible(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const int32_t *begin,
                                const int32_t *end);
 
+/* 1 if the one-pass kernels that have the form (the three-step Jacobi pass of examg_jacobi3; the Jacobi pair of examg_jacobi2 /
+ * examg_jacobi2_boxes on boxes of 192 rows and 8.4 * 10^6 points and more) fuse the six off-centre products of this stencil into their sums: a constant 7-point star in one of the two canonical entry orders whose six off-centre coefficients are
+ * all finite, non-zero and of magnitude exactly 2^e, e >= 0 (1/h^2 of every power-of-two grid; -1.0).  Such a product c * x is exact, so
+ * acc + c * x and fma(c, x, acc) round the same number once: the pass stays bit-identical to the loops for all inputs whose products
+ * c * x are finite.  Beyond 2^1024 a fused product can survive where a separate one became inf; NaN payloads are not compared.  The
+ * centre product and c + w * (f - acc) are never fused.  0 for every other stencil: separate products and sums, as in the loops. */
+int examg_pow2_fma_eligible(const examg_stencil_t *st);
+
 /* One Jacobi step on [begin,end) and the residual of its result in ONE pass: u_out = J(u_in), res = rhs - A u_out on the box (the
  * last pre-smoothing `Smoother@current` + `Residual@current = RHS - Laplace * Solution`, Testing/SISC/3D_VarCoeff.exa4:141-153,
  * Benchmark/Poisson3D/3D_FD_Poisson_fromL4.exa4:215-219).  27-entry stencil fields in the record layout (EXAMG_CLAYOUT_ENTRY_FASTEST,

@@ -37,6 +37,8 @@ cases = {
     "residual + restriction": lambda o: o.residual_restrict(Ls, u, Fs, f, Ls, None, A, Fcs, fcz, 1.0, b, e, [1, 1, 1], [n // 2] * 3),
     "one Jacobi step": lambda o: o.stencil_op(2, Ls, u, Fs, f, Ls, un, A, w, -1, b, e),
     "residual": lambda o: o.stencil_op(1, Ls, u, Fs, f, Ls, un, A, 0.0, -1, b, e),
+    "three Jacobi steps": lambda o: o.jacobi3(Ls, u, un, None, Fs, f, A, w, b, e),
+    "three colour loops": lambda o: o.rbgs_colours3(Ls, u, un, Fs, f, A, w, 0, b, e),
     "two Jacobi steps": lambda o: o.jacobi2(Ls, u, un, None, Fs, f, A, w, b, e),
     "fused red-black sweep": lambda o: o.rbgs_sweep_fused(Ls, u, un, Fs, f, A, w, 0, b, e),
     "correction + sweep": lambda o: o.rbgs_sweep_fused_prolong(Ls, u, un, Fs, f, A, w, 0, b, e, Lc, uc),

@@ -13,6 +13,7 @@ extern "C" int examg_jacobi3(const examg_layout_t *, const double *, double *, d
 extern "C" int examg_rbgs_colours3(const examg_layout_t *, const double *, double *, const examg_layout_t *, const double *, const examg_stencil_t *, double, int,
                                    const int32_t *, const int32_t *, examg_stream_t) { return 1; }
 extern "C" int examg_three_stage_eligible(const examg_layout_t *, const examg_layout_t *, const examg_stencil_t *, const int32_t *, const int32_t *) { return 0; }
+extern "C" int examg_pow2_fma_eligible(const examg_stencil_t *) { return 0; }
 EOF
 (cd $T && hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fPIC -shared -std=c++17 -Wno-unused-function -o $R/tools/lab/libexamg_r4a.so exastencils_amd/csrc/*.hip exastencils_amd/csrc/*.cpp -ldl)
 rm -rf $T; ls -la $R/tools/lab/libexamg_r4a.so

@@ -72,9 +72,10 @@ from .exa4_builtins import Builtins  # noqa: E402
 from .exa4_fusion import LazyFusions  # noqa: E402
 from .exa4_peepholes import Peepholes  # noqa: E402
 from .exa4_conservation import Conservation, _EXPR, expand  # noqa: E402
+from .exa4_complex import ComplexFields  # noqa: E402
 
 
-class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonlinear, Conservation):
+class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonlinear, Conservation, ComplexFields):
     """One ExaSlang-4 program bound to a kernel layer (`ops`: HipOps on the GPU), a block decomposition and a
     communicator.  `run()` executes `Function Application`; printed lines are collected in `self.out`."""
 
@@ -158,6 +159,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         self._bc_epoch: Dict[Tuple[str, int], int] = {}
         self._pair_tmp: Dict[Tuple[str, int], Field] = {}
         self._bc_valid = set()      # (field, level, slot) whose physical-boundary planes hold the field's Dirichlet values
+        self._complex_names = set() # fields declared on a Complex<Real> layout (exa4_complex.py)
+        self._complex_scratch: Dict[int, Field] = {}     # per level: the real field a `C = <real point expression>` loop fills first
+        self._bc_depth = 0          # inside a boundary function that `apply bc` runs
         self._cell_names = set()    # fields declared on a cell layout: never taken by a one-pass peephole or cross-statement fusion
         self._lazy_init()           # pending loops of the cross-statement fusions (exastencils_amd/exa4_fusion.py)
         self._declare()
@@ -207,6 +211,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             ld = layouts.get(fd.layout)
             if ld is None:
                 raise Exa4SyntaxError("field %s uses the undeclared layout %s" % (fd.name, fd.layout))
+            if ld.datatype == "Complex":
+                self._declare_complex_field(fd, ld, nslots[fd.name], sfield_fields)
+                continue
             if ld.localization not in ("Node", "Cell"):
                 raise Exa4Unsupported("layout %s: localization %s (node and cell fields only)" % (ld.name, ld.localization))
             if ld.vec_len != 1 and fd.name not in sfield_fields:
@@ -251,6 +258,12 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                 self.transfer[sd.name] = sd.transfer
                 self.transfer_factor[sd.name] = float(sd.transfer_factor)
         self._stencil_decls = {s.name: s for s in a.stencils if not s.transfer}
+        # a name declared once per level (`Stencil A@3 {..}  Stencil A@4 {..}`: the layer-4 text generated from layer 3)
+        self._stencil_decl_at = {}
+        for sd in a.stencils:
+            if not sd.transfer and sd.levels is not None:
+                for lvl in self.levels_of(sd.levels):
+                    self._stencil_decl_at.setdefault((sd.name, lvl), sd)
         for sf in a.sfields:
             sd = self._stencil_decls.get(sf.stencil)
             if sd is None:
@@ -435,6 +448,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         """The named scalar fields under `[x, y, z] => [x / 2, y, z, x % 2]`: their (still zero) arrays are re-allocated in the split
         layout.  Only where the kernel layer has transformed layouts (HipOps: examg_transform_field); the CPU stand-in of the tests
         keeps the directive recorded."""
+        for fname, lvls in self._transform_items(items):
+            if fname in self._complex_names:      # whatever the kernel layer: the complex kernels take untransformed layouts
+                raise Exa4Unsupported("field %s: the colour-split layout of a complex field" % fname)
         if not hasattr(self.ops, "transform_field"):
             return
         for fname, lvls in self._transform_items(items):
@@ -473,7 +489,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
     def _stencil_planes(self, name: str, lvl: int) -> Stencil:
         s = self.stencils.get((name, lvl))
         if s is None:
-            sd = self._stencil_decls.get(name)
+            sd = self._stencil_decl_at.get((name, lvl)) or self._stencil_decls.get(name)
             if sd is None:
                 raise Exa4SyntaxError("stencil %s is not declared" % name)
             if lvl not in self.levels_of(sd.levels):
@@ -491,7 +507,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                 s.c_struct(self.ops)      # the tables go to the device here, never inside a recording
                 return s
             offs = [tuple(o) + (0,) * (3 - len(o)) for o, _ in sd.entries]
-            s = self.stencils[(name, lvl)] = Stencil(offs, [float(self._eval(e, fr)) for _, e in sd.entries])
+            vals = [self._eval(e, fr) for _, e in sd.entries]      # entries over complex globals stay complex (exa4_complex.py)
+            s = self.stencils[(name, lvl)] = Stencil(offs, [v if isinstance(v, complex) and v.imag != 0.0 else float(complex(v).real) for v in vals])
+            s.has_complex_entries = any(isinstance(c, complex) for c in s.coefs)
         return s
 
     @staticmethod
@@ -750,6 +768,15 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                 reads |= self._globals_below(self._coef_expr(n[1]), seen)[0]
             elif len(n) == 4 and n[0] == "assign" and isinstance(n[2], tuple) and n[2][0] == "id" and n[2][1] in self.globals:
                 assigned.add(n[2][1])
+            elif len(n) == 2 and n[0] == "applybc" and isinstance(n[1], tuple) and n[1][0] == "fld":
+                for (fname, _), f in self.fields.items():      # `apply bc` of a field with a boundary function runs that function
+                    bf = getattr(f, "bc_function", None)
+                    if fname == n[1][1] and bf is not None and bf not in seen:
+                        seen.add(bf)
+                        for fn in self.functions[bf]:
+                            r, a = self._globals_below(("block", list(fn.body)), seen)
+                            reads |= r
+                            assigned |= a
             elif len(n) == 4 and n[0] == "call" and n[1] in self.functions and n[1] not in seen:
                 seen.add(n[1])
                 for fn in self.functions[n[1]]:
@@ -1035,6 +1062,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             if s[1] == "finish":
                 return
             f, slot = self._field(s[3], fr)
+            if f.layout.is_complex:      # one block without periodic axes (checked where the field is declared): nothing to exchange
+                return
             self.comm.exchange(f, slot, s[2])
         elif k == "applybc":
             f, slot = self._field(s[1], fr)
@@ -1160,6 +1189,13 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                 self.launches += 1
                 self.ops.apply_bc_cell(f.lc, f.data(slot), self.domain.geom(f.level), f.cell_bc[0], f.cell_bc[1], mask)
             return
+        if getattr(f, "bc_function", None) is not None:      # a boundary function of a complex node field (exa4_complex.py)
+            self._bc_depth += 1
+            try:
+                self.call(f.bc_function, f.level)
+            finally:
+                self._bc_depth -= 1
+            return
         if f.bc_fn is None:
             return
         if self.fuse and (f.name, f.level, slot) in self._bc_valid:
@@ -1249,6 +1285,14 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         ghost = self._recognise_ghost_loop(s, f, fr)      # a boundary function's loop over one face (exa4_conservation.py)
         if ghost is not None:
             return self._launch(ghost, None, None, None)
+        if f.layout.is_complex and only is not None:
+            return self._exec_complex_only_loop(s, f, fr)
+        if only is not None and not f.layout.is_cell and any(n and n[0] == "off" and n[1][0] == "fld" for n in _walk(("block", list(body)))):
+            raise Exa4Unsupported("loop over %s only %s %s: an offset access in a loop over a region of a real node field (boundary functions "
+                                  "exist for cell fields and complex node fields)" % (f.name, only[0], list(only[1])))
+        if f.layout.is_complex and (where is not None or fr.mcolour is not None):
+            raise Exa4Unsupported("loop over complex field %s %s" % (f.name, "with a `where` condition" if where is not None else
+                                                                      "under a multi-colouring (color with several expressions)"))
         if self._check_cell_body(body, fr) and not f.layout.is_cell:
             raise Exa4Unsupported("loop over node field %s with a body over cell fields" % f.name)
         if f.layout.is_cell and (only is not None or fr.contract is not None):
@@ -1316,6 +1360,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             if op == "+" and st[1] == "+=" and rhs[0] == "bin" and rhs[1] == "*" and rhs[2][0] == "fld" and rhs[3][0] == "fld":
                 X, xs = self._field(rhs[2], fr)
                 Y, ys = self._field(rhs[3], fr)
+                if X.layout.is_complex or Y.layout.is_complex:
+                    fr.vars[var] = fr.vars[var] + self._complex_dot(X, xs, Y, ys, boxes)
+                    continue
                 acc = 0.0
                 for b, e in boxes:
                     self.launches += 1

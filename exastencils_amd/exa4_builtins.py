@@ -36,6 +36,8 @@ class Builtins:
         if not pos:
             raise Exa4Unsupported("%s without a field argument" % name)
         f, slot = self._field(args[pos[0]], fr)
+        if f.layout.is_complex:
+            raise Exa4Unsupported("%s of complex field %s: field I/O of complex type" % (name, f.name))
         fname = str(self._eval(args[0], fr)).replace("$blockId", str(self.domain.rank))
         rest = [self._eval(a, fr) for a in args[pos[0] + 1:]]
         if iface in ("hdf5", "nc", "mpiio", "sion"):

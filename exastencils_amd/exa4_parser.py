@@ -12,6 +12,7 @@ AST: tuples.  Expressions: ("num", v) ("str", s) ("id", name, level) ("fld", nam
 ("range", a, b) ("list", items) ("but", spec, spec)."""
 from __future__ import annotations
 
+import cmath
 import math
 import re
 from dataclasses import dataclass, field as _dcf
@@ -30,7 +31,7 @@ class Exa4Unsupported(NotImplementedError):
 # =====================================================================================================================
 _TOKEN = re.compile(r"""
     (?P<ws>\s+|//[^\n]*|/\*.*?\*/)
-  | (?P<num>(?:\d+\.\d*|\.\d+|\d+)(?:[eE][+-]?\d+)?)
+  | (?P<num>(?:\d+\.\d*|\.\d+|\d+)(?:[eE][+-]?\d+)?(?:j\b)?)
   | (?P<id>[A-Za-z_][A-Za-z0-9_]*)
   | (?P<str>"[^"\n]*"|'[^'\n]*')
   | (?P<op>=>|\*\*|\+=|-=|\*=|/=|==|!=|<=|>=|&&|\|\||[@()\[\]{}<>,:=+\-*/%!.])
@@ -115,7 +116,11 @@ _STMT_WORDS = {"loop", "communicate", "apply", "advance", "repeat", "if", "Var",
                "begin", "finish", "print"}
 _SLOT_WORDS = {"active", "activeSlot", "current", "currentSlot", "next", "nextSlot", "previous", "previousSlot"}
 _LEVEL_WORDS = {"current", "coarser", "finer", "finest", "coarsest", "all"}
-_MATH = {"sqrt": math.sqrt, "fabs": abs, "abs": abs, "sin": math.sin, "cos": math.cos, "tan": math.tan, "exp": math.exp,
+def _sqrt(x):
+    return cmath.sqrt(x) if isinstance(x, complex) else math.sqrt(x)
+
+
+_MATH = {"sqrt": _sqrt, "fabs": abs, "abs": abs, "sin": math.sin, "cos": math.cos, "tan": math.tan, "exp": math.exp,
          "sinh": math.sinh, "cosh": math.cosh, "tanh": math.tanh, "log": math.log, "pow": math.pow, "max": max, "min": min,
          "floor": math.floor, "ceil": math.ceil, "ldexp": lambda x, e: math.ldexp(float(x), int(e)), "fmod": math.fmod,
          "asin": math.asin, "acos": math.acos, "atan": math.atan, "atan2": math.atan2, "log10": math.log10}
@@ -147,6 +152,7 @@ class Parser:
         self.sfields: List[StencilFieldDecl] = []
         self.globals: List[Tuple[str, object]] = []
         self.functions: List[FunctionDecl] = []
+        self.equations: List[Tuple[str, object, object, object]] = []      # (name, levels, lhs, rhs)
 
     # -- token helpers --------------------------------------------------------------------------------------------
     def peek(self, k: int = 0) -> Tok:
@@ -194,6 +200,8 @@ class Parser:
                 self._stencil_field()
             elif t.text == "Globals":
                 self._globals()
+            elif t.text == "Equation":
+                self._equation()
             elif t.text == "LayoutTransformations":
                 self._layout_transformations()
             elif t.text in ("Function", "Func", "Def", "noinline"):
@@ -201,6 +209,19 @@ class Parser:
             else:
                 raise Exa4SyntaxError("line %d: unexpected %r at top level" % (t.line, t.text))
         return self
+
+    def _equation(self):
+        """`Equation name@L { lhs == rhs }` (solver/l4/L4_EquationDecl.scala): parsed and kept; the layer-4 text of the reference's programs
+        spells the equation out again wherever `solve locally` uses it."""
+        self.expect("Equation")
+        name = self.ident()
+        levels = self.decl_levels()
+        self.expect("{")
+        eq = self.expr()
+        self.expect("}")
+        if eq[0] != "bin" or eq[1] != "==":
+            raise Exa4SyntaxError("Equation %s: `lhs == rhs` expected" % name)
+        self.equations.append((name, levels, eq[2], eq[3]))
 
     def _bad_comm(self):
         t = self.peek()
@@ -256,7 +277,12 @@ class Parser:
         name = self.ident()
         self.expect("<")
         dt, vec = self.ident(), 1
-        if self.accept("<"):        # ColumnVector<Real,7>
+        if dt == "Complex" and self.accept("<"):      # Complex<Real> | Complex<Double>: (re, im) per point
+            inner = self.ident()
+            if inner not in ("Real", "Double"):
+                raise Exa4Unsupported("layout %s: Complex<%s> (double precision only)" % (name, inner))
+            self.expect(">")
+        elif self.accept("<"):        # ColumnVector<Real,7>
             self.ident()
             self.expect(",")
             vec = int(self.next().text)
@@ -336,7 +362,11 @@ class Parser:
                 self.expect("with")
                 mapped.append((src, self.expr()))
             self.accept(",")
-        if mapped:
+        if mapped and _same_level_offsets(mapped) is not None:
+            # `[i0, i1] from [(i0 - 1.0), i1] with c`: the mapped spelling of an offset entry (how the layer-4 text generated from layer 3
+            # writes every stencil, Examples/Helmholtz/2D_FD_Helmholtz_fromL3)
+            d.entries += [(off, w) for off, (_, w) in zip(_same_level_offsets(mapped), mapped)]
+        elif mapped:
             d.transfer, d.transfer_factor = _classify_transfer(mapped, with_factor=True)
         self.stencils.append(d)
 
@@ -640,7 +670,7 @@ class Parser:
             reduction = (op, self.ident())
             self.expect(")")
         # the body of a ghost loop on the boundary may read its field at the cell inside (`hu = -hu@[1, 0]`: a boundary function)
-        saved, self._ghost_body = self._ghost_body, only is not None and only[0] == "ghost" and only[2]
+        saved, self._ghost_body = self._ghost_body, only is not None and only[0] in ("ghost", "dup") and only[2]
         try:
             body = self.block()
         finally:
@@ -721,6 +751,8 @@ class Parser:
         if t.kind != "id":
             raise Exa4SyntaxError("line %d: unexpected %r in an expression" % (t.line, t.text))
         name = t.text
+        if name.startswith("vf_") and name[-2:] in ("_0", "_1", "_2") and name not in self.field_names:
+            name = name[:-1] + "xyz"[int(name[-1])]      # `vf_nodePosition_0`: the numbered spelling of the layer-4 text generated from layer 3
         if name in ("true", "false"):
             return ("num", name == "true")
         slot = None
@@ -745,12 +777,17 @@ class Parser:
             if name.startswith("vf_") and name not in self.field_names:
                 # a virtual field of the grid at a neighbouring cell / node: `vf_cellWidth_x@[-1, 0, 0]` (grid/l4/L4_VirtualFieldAccess.scala)
                 self.next()
-                return ("vfo", name, level, tuple(int(_const_value(e)) for e in self._const_list()))
-            if not (name in self.expr_names or (name in self.field_names and self._ghost_body)):
-                raise Exa4Unsupported("line %d: offset access %s@[...]" % (t.line, name))
+                voff = tuple(int(_const_value(e)) for e in self._const_list())
+                return ("vfo", name, level, voff) if any(voff) else ("id", name, level)
+            mark = self.p
             self.next()
             off = tuple(int(_const_value(e)) for e in self._const_list())
             off = off + (0,) * (3 - len(off))
+            if not any(off) and (name in self.field_names or name in self.stencil_names or name in self.sfield_names):
+                off = None      # `u@5@[0, 0]`: the point of the loop itself (the generated layer-4 text writes it out)
+            elif not (name in self.expr_names or (name in self.field_names and self._ghost_body)):
+                self.p = mark
+                raise Exa4Unsupported("line %d: offset access %s@[...]" % (t.line, name))
         if off is not None:
             return ("off", ("fld", name, slot, level) if name in self.field_names else ("id", name, level), off)
         if name in self.field_names:
@@ -772,6 +809,8 @@ class Parser:
 
 
 def _num(text: str, sign: int):
+    if text.endswith("j"):          # the imaginary part of a complex literal `(0.0+1.0j)`: the sum is evaluated like any other
+        return ("num", complex(0.0, sign * float(text[:-1])))
     if re.fullmatch(r"\d+", text):
         return ("num", sign * int(text))
     return ("num", sign * float(text))
@@ -827,6 +866,15 @@ def _arith(op: str, a, b):
     if op == "||":
         return bool(a) or bool(b)
     raise Exa4SyntaxError("operator %r" % op)
+
+
+def _same_level_offsets(mapped):
+    """The integer offsets of mapped entries whose sources are i_d + constant in every dimension, None for anything else."""
+    at0 = [tuple(float(_const_value(e, {"i0": 0.0, "i1": 0.0, "i2": 0.0})) for e in src) for src, _ in mapped]
+    at1 = [tuple(float(_const_value(e, {"i0": 1.0, "i1": 1.0, "i2": 1.0})) for e in src) for src, _ in mapped]
+    if all(b - a == 1.0 and a == int(a) for o0, o1 in zip(at0, at1) for a, b in zip(o0, o1)):
+        return [tuple(int(a) for a in o0) for o0 in at0]
+    return None
 
 
 def _classify_transfer(mapped, with_factor: bool = False):

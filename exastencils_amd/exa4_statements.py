@@ -109,6 +109,8 @@ class Statements:
                 if sd is not None and any(self._reads_grid(e) and _contains(e, ("fld",)) for _, e in sd.entries):
                     raise Exa4Unsupported("stencil %s: a field in an entry of a stencil over the grid's virtual fields" % n[1])
         k = self._recognise_plain(st, fr, colour)
+        if getattr(k.A, "has_complex_entries", False) and not k.kind.startswith("c_"):      # (flagged where the stencil is built: exa4.py)
+            raise Exa4Unsupported("a stencil with complex entries on real field %s: real and complex mixed in one loop body" % k.D.name)
         if k.A is not None and getattr(k.A, "is_axis", False):
             if k.kind not in ("residual", "apply", "smooth"):
                 raise Exa4Unsupported("a stencil over the grid's virtual fields in a %s statement" % k.kind)
@@ -127,6 +129,10 @@ class Statements:
         if lhs[0] != "fld":
             raise Exa4Unsupported("loop body assigns to %s" % lhs[0])
         D, ds = self._field(lhs, fr)
+        if D.layout.is_complex or self._reads_complex(rhs):      # complex fields: the kinds c_* (exa4_complex.py)
+            if self._names_coef_expr(rhs):
+                raise Exa4Unsupported("semilinear operator (coefficient-expression stencil) on complex field %s" % D.name)
+            return self._recognise_complex(op, lhs, rhs, D, ds, fr)
         if self._names_coef_expr(rhs):
             return self._recognise_nonlinear(op, lhs, rhs, D, ds, colour, fr)
         if op == "=":
@@ -246,6 +252,8 @@ class Statements:
         """Issue the loop `k` stands for on the box [b, e): the only kernel-layer calls of loop-body assignments, and their count."""
         ops, kind = self.ops, k.kind
         D, U, F = k.D, k.U, k.F
+        if kind.startswith("c_"):             # (exa4_complex.py) a loop over complex fields
+            return self._launch_complex(k, b, e, colour)
         if kind == "bc_face":                 # (exa4_conservation.py) one face of a boundary function; no face: the block has a neighbour there
             if k.prog[1]:
                 self.launches += 1
@@ -331,6 +339,8 @@ class Statements:
         (examg_stencil_op_coloured); False for every other kind."""
         what = "under a multi-colouring (color with several expressions)"
         D, U, F = k.D, k.U, k.F
+        if k.kind.startswith("c_"):
+            raise Exa4Unsupported("complex field %s %s" % (D.name, what))
         for X in (D, F, U) if k.kind == "residual" else (D, U, F):      # in the order the statement names them
             if X is not None and X.layout.transform:
                 raise Exa4Unsupported("colour-split field %s %s" % (X.name, what))

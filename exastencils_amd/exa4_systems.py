@@ -138,6 +138,10 @@ class Systems:
     def _exec_solve_locally(self, st, boxes, colour, fr):
         """`solve locally [relax w] { F_c => row_c == rhs_c .. }` in a coloured loop: one examg_sys_relax per box."""
         _, jacobi, relax, rows = st
+        if len(rows) == 1 and rows[0][0][0] == "fld" and self._field(rows[0][0], fr)[0].layout.is_complex:
+            return self._exec_complex_solve(st, boxes, colour, fr)      # one complex node unknown: EXAMG_CRELAX (exa4_complex.py)
+        if any(u[0] == "fld" and self._field(u, fr)[0].layout.is_complex for u, _, _ in rows):
+            raise Exa4Unsupported("solve locally with more than one unknown over complex fields (the system path knows real cell fields)")
         if jacobi:
             raise Exa4Unsupported("solve locally with jacobi")
         if colour is None:

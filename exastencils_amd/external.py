@@ -16,6 +16,10 @@ from .layout import FieldLayout
 
 class ExternalField:
     def __init__(self, name: str, layout: FieldLayout, target: Field, ops):
+        if layout.is_complex or target.layout.is_complex:
+            from .exa4_parser import Exa4Unsupported
+
+            raise Exa4Unsupported("external field %s on %s: external fields of complex type (the copy kernels move real fields)" % (name, target.name))
         self.name, self.layout, self.target, self.ops = name, layout, target, ops
         self.lc = layout.c_struct()
         self._stage = None

@@ -32,7 +32,7 @@ class Field:
         self.name, self.level, self.layout, self.num_slots = name, level, layout, num_slots
         self.bc_fn, self.bc_params = bc_fn, tuple(bc_params)
         self.lc = layout.c_struct()
-        self.slots = [ops.new_array(layout.size) for _ in range(num_slots)]   # initFieldsWithZero
+        self.slots = [ops.new_array(layout.doubles) for _ in range(num_slots)]   # initFieldsWithZero; a complex layout: (re, im) per point
         self.current_slot = 0
 
     @property

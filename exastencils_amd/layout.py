@@ -31,10 +31,46 @@ class FieldLayout:
     # "node" | "cell": Python-side only.  The C struct is the same for both (a cell layout is the one without duplicate layers);
     # the localization travels as the choice of entry point (examg_*_cell).
     localization: str = "node"
+    # "real" | "complex": Python-side only, like the localization.  A point of a complex field is two consecutive doubles (re, im); every
+    # count of the layout stays in POINTS and the element kind travels as the choice of entry point (examg_c*: include/examg.h).
+    element: str = "real"
 
     @property
     def is_cell(self) -> bool:
         return self.localization == "cell"
+
+    @property
+    def is_complex(self) -> bool:
+        return self.element == "complex"
+
+    @property
+    def doubles(self) -> int:
+        """Doubles of an array of this layout: size points, two doubles each for a complex field."""
+        return (2 if self.is_complex else 1) * self.size
+
+    def as_complex(self) -> "FieldLayout":
+        from dataclasses import replace
+
+        if self.transform or self.is_cell:
+            raise ValueError("complex fields are node fields in the untransformed layout")
+        return replace(self, element="complex")
+
+    def real_view(self) -> "FieldLayout":
+        """A complex field seen as a real field: every x count doubled.  `set` to a real constant, copies and pack / unpack of a complex
+        field are the real entry points on this view, with the x bounds of the box doubled (real_view_box)."""
+        from dataclasses import replace
+
+        if not self.is_complex:
+            return self
+
+        def dx(t):
+            return (2 * t[0], t[1], t[2])
+
+        return replace(self, inner=dx(self.inner), ghost=dx(self.ghost), dup=dx(self.dup), pad_l=dx(self.pad_l), pad_r=dx(self.pad_r), element="real")
+
+    @staticmethod
+    def real_view_box(begin, end):
+        return [2 * begin[0], begin[1], begin[2]], [2 * end[0], end[1], end[2]]
 
     @staticmethod
     def cell(nd: int, ncells: Sequence[int], ghost: int, communicates_ghost: bool = True, align: int = 0) -> "FieldLayout":

@@ -131,6 +131,10 @@ FLUX_GATHER, FLUX_MARCH = 1, 2            # what examg_flux_route answers (-1 re
 FLUX_DEFAULT = FLUX_MARCH                 # the kernel examg_flux_step takes (the measured table decides it)
 REDUCE_MAX, REDUCE_MIN = 0, 1
 OP_FIELD0 = 32
+# ---- complex-valued node fields (include/examg.h: examg_cstencil_op and what follows it) --------------------------------------------------
+CRELAX = 3                                # the fourth loop kind of examg_cstencil_op, beside EXAMG_APPLY / RESIDUAL / SMOOTH
+CSTENCIL_GATHER, CSTENCIL_MARCH = 1, 2    # what examg_cstencil_route answers (-1 refused, 0 empty box)
+C_XPAY, C_XMAY, C_XPAYMBZ = 0, 1, 2       # the forms of examg_clincomb
 # `f<k>` pushes the value of input field k at the cell the program is evaluated at; no `u`, no position
 FLUX_OPS = dict((k, v) for k, v in NL_OPS.items() if k != "u")
 FLUX_OPS.update(("f%d" % k, OP_FIELD0 + k) for k in range(FLUX_MAX_FIELDS))
@@ -183,6 +187,8 @@ SYMBOLS = [
     "examg_gs_sweep", "examg_gs_route",
     "examg_axis_op", "examg_axis_route", "examg_fill_expr_grid", "examg_apply_dirichlet_expr_grid", "examg_max_err_expr_grid",
     "examg_flux_step", "examg_flux_route", "examg_reduce_expr_cell",
+    "examg_cstencil_op", "examg_cstencil_route", "examg_clincomb", "examg_cdot", "examg_crestrict", "examg_cprolong_add", "examg_cshift_div",
+    "examg_cfrom_parts",
 ]
 
 COMM_ID_BYTES = 128
@@ -327,6 +333,14 @@ def load(path=None):
     L.examg_flux_step.argtypes = [xp, ip, ip, vp]
     L.examg_flux_route.argtypes = [xp, ip, ip]
     L.examg_reduce_expr_cell.argtypes = [C.c_int, C.c_int, lp, C.POINTER(vp), np_, ip, ip, vp, vp, vp]
+    L.examg_cstencil_op.argtypes = [C.c_int, lp, vp, lp, vp, lp, vp, sp, dp, dp, C.c_int, ip, ip, vp]
+    L.examg_cstencil_route.argtypes = [C.c_int, lp, vp, lp, vp, lp, vp, sp, dp, dp, C.c_int, ip, ip]
+    L.examg_clincomb.argtypes = [C.c_int, lp, vp, lp, vp, lp, vp, lp, vp, dp, dp, ip, ip, vp]
+    L.examg_cdot.argtypes = [lp, vp, lp, vp, ip, ip, vp, vp, vp]
+    L.examg_crestrict.argtypes = [lp, vp, lp, vp, C.c_double, ip, ip, vp]
+    L.examg_cprolong_add.argtypes = [lp, vp, lp, vp, ip, ip, vp]
+    L.examg_cshift_div.argtypes = [lp, vp, ip, dp, ip, ip, vp]
+    L.examg_cfrom_parts.argtypes = [lp, vp, lp, vp, lp, vp, ip, ip, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("examg_version", "examg_last_error", "examg_device_count", "examg_reduce_work_bytes", "examg_exchange_workspace_bytes",
@@ -347,6 +361,9 @@ def load(path=None):
     if hasattr(L, "examg_debug_flux_route"):         # debug build only: examg_flux_step on the kernel named (0: the default)
         L.examg_debug_flux_route.argtypes = [C.c_int]
         L.examg_debug_flux_route.restype = C.c_int
+    if hasattr(L, "examg_debug_cstencil_route"):     # debug build only: examg_cstencil_op on the kernel named (0: the default), rows per wave
+        L.examg_debug_cstencil_route.argtypes = [C.c_int, C.c_int]
+        L.examg_debug_cstencil_route.restype = C.c_int
     if hasattr(L, "examg_debug_sys_narrow"):         # debug build only: the 8-byte form of the system kernels
         L.examg_debug_sys_narrow.argtypes = [C.c_int]
         L.examg_debug_sys_narrow.restype = C.c_int
@@ -375,6 +392,12 @@ def check(rc: int, what: str = ""):
 
 def ivec(v):
     return (C.c_int32 * 3)(*[int(x) for x in v])
+
+
+def dvec2(z):
+    """(re, im) of a Python number as the two doubles the complex entry points take."""
+    z = complex(z)
+    return (C.c_double * 2)(z.real, z.imag)
 
 
 def dvec4(v):

@@ -393,6 +393,73 @@ class HipOps:
                                             self.ptr(self._work), self._stream()), "examg_reduce_expr_cell")
         return out
 
+    # -- complex-valued node fields: arrays of 2 * size(layout) doubles, (re, im) per point -------------------------------------------
+    def new_complex_array(self, npoints: int):
+        """A zeroed complex field of npoints points: 2 * npoints doubles, 16-byte aligned (torch allocations are)."""
+        return self.new_array(2 * int(npoints))
+
+    def new_complex_scalar(self):
+        return self.torch.zeros(2, dtype=self.torch.float64, device=self.device)
+
+    def _cstencil(self, st: Stencil):
+        """examg_stencil_t with the real parts of the entries, and the array of their imaginary parts."""
+        real = Stencil(st.offsets, [complex(c).real for c in st.coefs], st.cfield, st.clayout, st.ctransform, st.wform)
+        im = (C.c_double * _lib.MAXE)(*[complex(c).imag for c in st.coefs])
+        return real.c_struct(self.ptr), im
+
+    def _cstencil_args(self, mode, lu, u, lf, rhs, ld, dst, st, w, colour, begin, end):
+        sc, im = self._cstencil(st)
+        return (int(mode), C.byref(lu), self.ptr(u), C.byref(lf) if lf is not None else None, self.ptr(rhs) if rhs is not None else None,
+                C.byref(ld) if ld is not None else None, self.ptr(dst) if dst is not None else None, C.byref(sc), im, _lib.dvec2(w), int(colour),
+                ivec(begin), ivec(end))
+
+    def cstencil_op(self, mode: int, lu, u, lf, rhs, ld, dst, st: Stencil, w, colour: int, begin, end):
+        """A loop over a constant stencil with complex entries on complex fields: mode 0 / 1 / 2 as stencil_op with a complex w, lib.CRELAX the
+        local solve of one colour in place on u (examg_cstencil_op)."""
+        check(self.L.examg_cstencil_op(*self._cstencil_args(mode, lu, u, lf, rhs, ld, dst, st, w, colour, begin, end), self._stream()),
+              "examg_cstencil_op")
+
+    def cstencil_route(self, mode: int, lu, u, lf, rhs, ld, dst, st: Stencil, w, colour: int, begin, end) -> int:
+        """What cstencil_op does with these arguments: -1 refused (the reason in examg_last_error), 0 empty box, lib.CSTENCIL_GATHER,
+        lib.CSTENCIL_MARCH."""
+        return int(self.L.examg_cstencil_route(*self._cstencil_args(mode, lu, u, lf, rhs, ld, dst, st, w, colour, begin, end)))
+
+    def clincomb(self, form: int, lx, x, ly, y, lz, z, ld, dst, a, b, begin, end):
+        """dst = x + a y (lib.C_XPAY), x - a y (lib.C_XMAY) or x + a (y - b z) (lib.C_XPAYMBZ), a and b complex (examg_clincomb)."""
+        check(self.L.examg_clincomb(int(form), C.byref(lx), self.ptr(x), C.byref(ly), self.ptr(y), C.byref(lz) if lz is not None else None,
+                                    self.ptr(z) if z is not None else None, C.byref(ld), self.ptr(dst), _lib.dvec2(a),
+                                    _lib.dvec2(b) if b is not None else None, ivec(begin), ivec(end), self._stream()), "examg_clincomb")
+
+    def cdot(self, lx, x, ly, y, begin, end, out=None):
+        """The unconjugated sum of x * y over the box; the two parts stay on the device (examg_cdot)."""
+        out = self.new_complex_scalar() if out is None else out
+        check(self.L.examg_cdot(C.byref(lx), self.ptr(x), C.byref(ly), self.ptr(y), ivec(begin), ivec(end), self.ptr(out), self.ptr(self._work),
+                                self._stream()), "examg_cdot")
+        return out
+
+    def complex_value(self, t) -> complex:
+        """Host value of a device complex scalar."""
+        v = t.tolist()
+        return complex(v[0], v[1])
+
+    def crestrict(self, lfine, rf, lc, fc, scale: float, begin, end):
+        check(self.L.examg_crestrict(C.byref(lfine), self.ptr(rf), C.byref(lc), self.ptr(fc), float(scale), ivec(begin), ivec(end), self._stream()),
+              "examg_crestrict")
+
+    def cprolong_add(self, lc, uc, lfine, uf, begin, end):
+        check(self.L.examg_cprolong_add(C.byref(lc), self.ptr(uc), C.byref(lfine), self.ptr(uf), ivec(begin), ivec(end), self._stream()),
+              "examg_cprolong_add")
+
+    def cshift_div(self, l, x, off, c, begin, end):
+        """x(i) = x(i + off) / c on the box: the absorbing-boundary assignment (examg_cshift_div)."""
+        check(self.L.examg_cshift_div(C.byref(l), self.ptr(x), ivec(off), _lib.dvec2(c), ivec(begin), ivec(end), self._stream()), "examg_cshift_div")
+
+    def cfrom_parts(self, l, dst, lre, re, lim, im, begin, end):
+        """dst = (re, im) from real fields; a part that is None is 0.0 (examg_cfrom_parts)."""
+        check(self.L.examg_cfrom_parts(C.byref(l), self.ptr(dst), C.byref(lre) if lre is not None else None, self.ptr(re) if re is not None else None,
+                                       C.byref(lim) if lim is not None else None, self.ptr(im) if im is not None else None, ivec(begin), ivec(end),
+                                       self._stream()), "examg_cfrom_parts")
+
     def scalar_value(self, t) -> float:
         """Host value of a device scalar (the reference's 8-byte D2H copy after a reduction)."""
         return float(t.item())

@@ -1002,6 +1002,99 @@ enum { EXAMG_REDUCE_MAX = 0, EXAMG_REDUCE_MIN = 1 };
 int examg_reduce_expr_cell(int op, int nfields, const examg_layout_t *l, const double *const *x, const examg_nlexpr_t *prog, const int32_t *begin,
                            const int32_t *end, double *result, void *work, examg_stream_t stream);
 
+/* ---- complex-valued node fields: `Layout X< Complex<Real>, Node >` (base/ir/IR_Datatype.scala:191-201: std::complex<double> per point;
+ * Examples/Helmholtz/2D_FD_Helmholtz_fromL3: BiCGStab preconditioned by a cycle on the complex shifted Laplacian).
+ * Data model.  A point of a complex field is two consecutive doubles (re, im); the array holds 2 * size(layout) doubles and starts 16-byte
+ * aligned, so every point is one 16-byte access.  examg_layout_t is unchanged: every count is in POINTS.  A complex field seen as a real
+ * field with every x count doubled (pad, ghost, dup, inner and the x bounds of a box) is a valid real layout: `set` to a real constant,
+ * copies and pack / unpack of complex fields are the real entry points on that view (same bits) -- there are no complex twins of those.
+ *
+ * Arithmetic of every entry point below: fp64, no contraction, on the parts.  For a coefficient c = (a, b) and a value v = (x, y)
+ *     c . v = (a * x, a * y)                       when b is exactly 0.0 (how `double * std::complex<double>` multiplies)
+ *     c . v = (a * x - b * y, a * y + b * x)       otherwise
+ * and for a divisor c = (cr, ci)
+ *     z / c = (zr / cr, zi / cr)                   when ci is exactly 0.0
+ *     z / c = ((zr * cr + zi * ci) / den, (zi * cr - zr * ci) / den),  den = cr * cr + ci * ci      otherwise.
+ * These are NOT the bits of libstdc++'s scaled operator/ (which divides by max(|cr|, |ci|) first); the reference's results file carries six
+ * digits.  Sums and differences are componentwise.
+ *
+ * examg_cstencil_op: a loop over a CONSTANT stencil (st->cfield NULL) whose offsets lie in {-1, 0, 1}^nd, nd = 2 or 3, any entry order.
+ * Entry k has the coefficient (st->coef[k], coef_im[k]); coef_im NULL: all imaginary parts 0.0.  w = (w[0], w[1]).
+ *     conv = c_0 . u(i + o_0);  conv = conv + c_k . u(i + o_k), k = 1 .. nent - 1 in declared order
+ *     EXAMG_APPLY     dst = conv
+ *     EXAMG_RESIDUAL  dst = rhs - conv
+ *     EXAMG_SMOOTH    dst = u + w . (rhs - conv)
+ *     EXAMG_CRELAX    `solve locally relax w { u => (A * u) == rhs }` with one unknown, in the form of solver/ir/IR_LocalDirectInvert.scala:
+ *                     126-136, in place on the points of one colour: off = the off-centre entries folded in declared order like conv (the
+ *                     centre entry st->diag skipped), b = rhs - off (b = rhs where there is no off-centre entry), x = b / c_centre,
+ *                     u = (u * (1.0 - w[0])) + (w[0] * x) on each part; w[0] == 1.0 gives u = x.  colour must be 0 or 1, w[1] must be 0.0,
+ *                     dst must be u (or NULL) and ld is not read.
+ * colour, the box, the per-argument layouts (u through lu, rhs through lf, dst through ld) and aliasing as for examg_stencil_op: -1 all
+ * points, else the points with (i0 + i1 + i2) % 2 == colour.  u and dst may be the same array only when colour >= 0 and every off-centre
+ * entry reaches a point of the other colour (the sum of its offsets is odd: star stencils, with or without all their entries); EXAMG_CRELAX
+ * needs such a stencil.  Only the points of the box (of the colour) are written, in dst alone.
+ * Refused before anything is launched, each with its own text: a null argument; a mode outside the four; nent outside 1 .. 27; a stencil
+ * field (st->cfield); a layout that is not 2-D or 3-D or is under a layout transformation; an offset outside {-1, 0, 1} or in a dimension
+ * the layouts do not have; an array that is not 16-byte aligned; a box that leaves the dst or rhs allocation, or that grown by the stencil's
+ * reach leaves the u allocation; dst == u without a colour or with an off-centre entry whose offsets sum to an even number; for EXAMG_CRELAX
+ * a colour other than 0 / 1, w[1] != 0.0, a dst other than u, such an entry, a st->diag that is not the (0, 0, 0) entry.  An empty box is a no-op that returns 0.
+ * Two kernels, the same bits.  EXAMG_CSTENCIL_GATHER: one lane per point, every entry read from memory; any admissible call.
+ * EXAMG_CSTENCIL_MARCH: star stencils of reach 1 with all 2 * nd + 1 entries (5-point in 2-D, 7-point in 3-D), any entry order, all four
+ * modes and colours: a wave owns 64 consecutive points of a row and marches in y (2-D) or z (3-D), one lane per point with 16-byte loads
+ * and stores, the three rows (planes) of u in registers, x neighbours from the adjacent lanes (the end lanes read theirs).
+ * examg_cstencil_route answers which one a call takes, nothing launched: -1 refused (text set), 0 empty box, else EXAMG_CSTENCIL_*. */
+#define EXAMG_CRELAX 3
+enum { EXAMG_CSTENCIL_GATHER = 1, EXAMG_CSTENCIL_MARCH = 2 };
+int examg_cstencil_op(int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs, const examg_layout_t *ld,
+                      double *dst, const examg_stencil_t *st, const double *coef_im, const double *w, int colour, const int32_t *begin,
+                      const int32_t *end, examg_stream_t stream);
+int examg_cstencil_route(int mode, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *rhs, const examg_layout_t *ld,
+                         const double *dst, const examg_stencil_t *st, const double *coef_im, const double *w, int colour, const int32_t *begin,
+                         const int32_t *end);
+
+/* The vector updates of BiCGStab on complex fields, evaluated in this association (a = (a[0], a[1]), b likewise; b is read by the last
+ * form only and may be NULL otherwise, as may lz / z):
+ *     EXAMG_C_XPAY     dst = x + a . y
+ *     EXAMG_C_XMAY     dst = x - a . y
+ *     EXAMG_C_XPAYMBZ  dst = x + a . (y - b . z)
+ * Each argument through its own layout; dst may be any of the operands (every point reads its own operands first).  Refused: null
+ * arguments, an unknown form, transformed layouts, misaligned arrays, a box that leaves an allocation. */
+enum { EXAMG_C_XPAY = 0, EXAMG_C_XMAY = 1, EXAMG_C_XPAYMBZ = 2 };
+int examg_clincomb(int form, const examg_layout_t *lx, const double *x, const examg_layout_t *ly, const double *y, const examg_layout_t *lz,
+                   const double *z, const examg_layout_t *ld, double *dst, const double *a, const double *b, const int32_t *begin,
+                   const int32_t *end, examg_stream_t stream);
+
+/* The UNCONJUGATED sum over the box of x . y (the reference's loops read `resHat * Residual`): result[0] = sum of (xr * yr) - (xi * yi),
+ * result[1] = sum of (xr * yi) + (xi * yr), every product rounded on its own and added on its own (2 K terms per part for K points).
+ * result: 2 doubles in device memory; work: examg_reduce_work_bytes() bytes.  A fixed tree: the same bits on every call with the same
+ * box.  An empty box gives (0.0, 0.0).  Refused: a null argument, layouts that are not 2-D or 3-D or are under a layout transformation, a
+ * misaligned array, a box that leaves the x or the y allocation. */
+int examg_cdot(const examg_layout_t *lx, const double *x, const examg_layout_t *ly, const double *y, const int32_t *begin, const int32_t *end,
+               double *result, void *work, examg_stream_t stream);
+
+/* The node transfer operators of examg_restrict and examg_prolong_add (real weights, 2-D and 3-D, `scale`; the same boxes, footprints and
+ * order of the terms) applied to each part: bit-equal to the real entry points run on the de-interleaved parts.  An empty box is a no-op that
+ * returns 0.  Refused, both: a null argument, layouts that are not 2-D or 3-D, of different dimensionality or under a layout transformation, a
+ * misaligned array.  examg_crestrict: a box that leaves the coarse allocation, a fine footprint [2 * begin - 1, 2 * (end - 1) + 1] that leaves
+ * the fine allocation.  examg_cprolong_add: a box that leaves the fine allocation, a negative fine index, a coarse footprint [begin / 2, end / 2]
+ * that leaves the coarse allocation. */
+int examg_crestrict(const examg_layout_t *lfine, const double *res_fine, const examg_layout_t *lcoarse, double *rhs_coarse, double scale,
+                    const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_cprolong_add(const examg_layout_t *lcoarse, const double *u_coarse, const examg_layout_t *lfine, double *u_fine, const int32_t *begin,
+                       const int32_t *end, examg_stream_t stream);
+
+/* x(i) = x(i + off) / c on the box, c = (c[0], c[1]): the absorbing-boundary assignment `u@[0,0] = u@[1,0] / (1 - (0+1j) * k * h)` of a
+ * boundary function.  Refused: a box that overlaps its own image shifted by off (off = 0 among them), a box or an image that leaves the
+ * allocation, an offset in a dimension the layout does not have, transformed layouts, a misaligned array. */
+int examg_cshift_div(const examg_layout_t *l, double *x, const int32_t *off, const double *c, const int32_t *begin, const int32_t *end,
+                     examg_stream_t stream);
+
+/* dst(i) = (re(i), im(i)) on the box from two REAL fields, each through its own layout; a NULL part is 0.0.  How `RHS = <real point
+ * expression>` reaches a complex field: examg_fill_expr into a real scratch field, then this call.  Refused: a box that leaves an allocation, a
+ * misaligned or transformed dst, a part whose layout has another dimensionality than dst. */
+int examg_cfrom_parts(const examg_layout_t *l, double *dst, const examg_layout_t *lre, const double *re, const examg_layout_t *lim, const double *im,
+                      const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

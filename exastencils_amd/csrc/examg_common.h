@@ -341,6 +341,117 @@ static inline bool check_stencil_box(const char *who, int mode, const examg_layo
   return true;
 }
 
+// ---- colourings (include/examg.h: examg_colouring_t), shared by the multi-colour stencil loops (kernels_multicolour.hip) and the
+// collective smoother of the block systems (kernels_blocksys.hip) ----------------------------------------------------------------------
+struct MCColour {
+  int nexpr;
+  int axes[3], shift[3], mod[3], rem[3];
+  int first[3], step[3], count[3];  // lattice per axis: i_d = first[d] + step[d] * j, j < count[d] (step 1: every point of the box)
+  int rowk;                         // expression that sets the start and the stride of a row (its axes include x), or -1
+  int row_w;                        // threads per row
+};
+
+__device__ __forceinline__ bool mc_member(const MCColour &c, int i0, int i1, int i2) {
+  bool ok = true;
+  for (int k = 0; k < c.nexpr; ++k) {
+    const int s = c.shift[k] + ((c.axes[k] & 1) ? i0 : 0) + ((c.axes[k] & 2) ? i1 : 0) + ((c.axes[k] & 4) ? i2 : 0);
+    ok = ok && (s % c.mod[k] == c.rem[k]);      // s >= 0 on the whole box (host check)
+  }
+  return ok;
+}
+
+// Thread t of mc_threads(col) -> its point of the colour in the box; false: the thread has none.  Expressions on a single axis are
+// iterated as a lattice, one expression over several axes that include x becomes a start and a stride per row, whatever is left is a
+// predicate: every expression is evaluated again on the point the lattice arrives at.  In two steps -- lattice row `row` of
+// mc_rows(col) -> (i1, i2), then place c0 < col.row_w of that row -> i0 -- for kernels that give a lane several rows.
+__device__ __forceinline__ void mc_row(const MCColour &col, long long row, int &i1, int &i2) {
+  i1 = col.first[1] + col.step[1] * (int)(row % col.count[1]);
+  i2 = col.first[2] + col.step[2] * (int)(row / col.count[1]);
+}
+__device__ __forceinline__ bool mc_place(const MCColour &col, const Box &box, int c0, int i1, int i2, int &i0) {
+  if (col.rowk >= 0) {
+    // (shift + i0 + the other summands) % n == rem: the first such i0 >= box.b0, then every n-th
+    const int k = col.rowk, n = col.mod[k];
+    const int s = col.shift[k] + box.b0 + ((col.axes[k] & 2) ? i1 : 0) + ((col.axes[k] & 4) ? i2 : 0);
+    i0 = box.b0 + (col.rem[k] - s % n + n) % n + n * c0;
+  } else {
+    i0 = col.first[0] + col.step[0] * c0;
+  }
+  return i0 < box.e0 && mc_member(col, i0, i1, i2);
+}
+__device__ __forceinline__ bool mc_point(const MCColour &col, const Box &box, long long t, int &i0, int &i1, int &i2) {
+  const long long row = t / col.row_w;
+  mc_row(col, row, i1, i2);
+  return mc_place(col, box, (int)(t - row * col.row_w), i1, i2, i0);
+}
+__host__ __device__ static inline long long mc_rows(const MCColour &c) { return (long long)c.count[1] * c.count[2]; }
+__host__ __device__ static inline long long mc_threads(const MCColour &c) { return (long long)c.row_w * c.count[1] * c.count[2]; }
+
+static inline const char *check_colouring(const examg_colouring_t *col, int nd, bool with_rem) {
+  if (col->nexpr < 1 || col->nexpr > 3) return "nexpr must be 1, 2 or 3";
+  for (int k = 0; k < col->nexpr; ++k) {
+    if (col->mod[k] <= 0) return "mod must be positive";
+    if (col->axes[k] <= 0 || col->axes[k] >= (1 << nd)) return "axes must name a non-empty set of the layout's axes";
+    if (with_rem && (col->rem[k] < 0 || col->rem[k] >= col->mod[k])) return "rem must lie in [0, mod)";
+  }
+  return nullptr;
+}
+
+static inline bool starts_nonnegative(const examg_colouring_t *col, const int32_t *begin) {
+  for (int k = 0; k < col->nexpr; ++k) {
+    long long s = col->shift[k];
+    for (int d = 0; d < 3; ++d)
+      if (col->axes[k] & (1 << d)) s += begin[d];
+    if (s < 0) return false;
+  }
+  return true;
+}
+
+// does some expression of the colouring change over the offset o?  (A colouring decouples a stencil when this holds for every entry off the centre.)
+static inline bool colouring_separates(const examg_colouring_t *col, const int32_t *o) {
+  for (int k = 0; k < col->nexpr; ++k) {
+    int s = 0;
+    for (int d = 0; d < 3; ++d)
+      if (col->axes[k] & (1 << d)) s += o[d];
+    if (s % col->mod[k] != 0) return true;
+  }
+  return false;
+}
+
+// the colour `col` on the box as the kernels iterate it (the colouring has passed check_colouring and starts_nonnegative)
+static inline MCColour make_colour(const examg_colouring_t *col, const Box &box) {
+  MCColour c;
+  c.nexpr = col->nexpr;
+  for (int k = 0; k < 3; ++k) {
+    const bool on = k < col->nexpr;
+    c.axes[k] = on ? col->axes[k] : 0;
+    c.shift[k] = on ? col->shift[k] : 0;
+    c.mod[k] = on ? col->mod[k] : 1;
+    c.rem[k] = on ? col->rem[k] : 0;
+  }
+  const int bb[3] = {box.b0, box.b1, box.b2}, ee[3] = {box.e0, box.e1, box.e2};
+  for (int d = 0; d < 3; ++d) {
+    c.first[d] = bb[d];
+    c.step[d] = 1;
+    for (int k = 0; k < col->nexpr; ++k)
+      if (col->axes[k] == (1 << d) && c.step[d] == 1 && col->mod[k] > 1) {      // the first single-axis expression of the axis
+        const int n = col->mod[k];
+        c.step[d] = n;
+        c.first[d] = bb[d] + (col->rem[k] - (col->shift[k] + bb[d]) % n + n) % n;
+      }
+    c.count[d] = c.first[d] < ee[d] ? (ee[d] - c.first[d] + c.step[d] - 1) / c.step[d] : 0;
+  }
+  c.rowk = -1;
+  c.row_w = c.count[0];
+  if (c.step[0] == 1)
+    for (int k = 0; k < col->nexpr && c.rowk < 0; ++k)
+      if ((col->axes[k] & 1) && col->axes[k] != 1 && col->mod[k] > 1) {
+        c.rowk = k;
+        c.row_w = (box.n0() + col->mod[k] - 1) / col->mod[k];
+      }
+  return c;
+}
+
 struct Params4 {
   double v[4];
 };

@@ -35,44 +35,14 @@ struct MCStencil {
   int wdiv;
 };
 
-struct MCColour {
-  int nexpr;
-  int axes[3], shift[3], mod[3], rem[3];
-  int first[3], step[3], count[3];  // lattice per axis: i_d = first[d] + step[d] * j, j < count[d] (step 1: every point of the box)
-  int rowk;                         // expression that sets the start and the stride of a row (its axes include x), or -1
-  int row_w;                        // threads per row
-};
-
-__device__ __forceinline__ bool mc_member(const MCColour &c, int i0, int i1, int i2) {
-  bool ok = true;
-  for (int k = 0; k < c.nexpr; ++k) {
-    const int s = c.shift[k] + ((c.axes[k] & 1) ? i0 : 0) + ((c.axes[k] & 2) ? i1 : 0) + ((c.axes[k] & 4) ? i2 : 0);
-    ok = ok && (s % c.mod[k] == c.rem[k]);      // s >= 0 on the whole box (host check)
-  }
-  return ok;
-}
-
 template <int MODE>
 __global__ void __launch_bounds__(256)
 k_stencil_coloured(LayoutDev lu, const double *u, LayoutDev lf, const double *__restrict__ rhs, LayoutDev ld, double *dst, LayoutDev lc,
                    MCStencil st, double w, MCColour col, Box box) {
-  const long long rows = (long long)col.count[1] * col.count[2];
-  const long long total = rows * col.row_w;
+  const long long total = mc_threads(col);
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
-    const long long row = t / col.row_w;
-    const int c0 = (int)(t - row * col.row_w);
-    const int i1 = col.first[1] + col.step[1] * (int)(row % col.count[1]);
-    const int i2 = col.first[2] + col.step[2] * (int)(row / col.count[1]);
-    int i0;
-    if (col.rowk >= 0) {
-      // (shift + i0 + the other summands) % n == rem: the first such i0 >= box.b0, then every n-th
-      const int k = col.rowk, n = col.mod[k];
-      const int s = col.shift[k] + box.b0 + ((col.axes[k] & 2) ? i1 : 0) + ((col.axes[k] & 4) ? i2 : 0);
-      i0 = box.b0 + (col.rem[k] - s % n + n) % n + n * c0;
-    } else {
-      i0 = col.first[0] + col.step[0] * c0;
-    }
-    if (i0 >= box.e0 || !mc_member(col, i0, i1, i2)) continue;
+    int i0, i1, i2;
+    if (!mc_point(col, box, t, i0, i1, i2)) continue;
     const long long iu = lidx_plain(lu, i0, i1, i2);
     double acc;
     if (st.cfield) {
@@ -164,38 +134,11 @@ k_mcgs_rowpair27(LayoutDev lu, double *u, LayoutDev lf, const double *__restrict
 
 static thread_local int g_mc_per_colour = 0;      // examg_debug_mcgs_per_colour (debug build): the sweep as its colour loops
 
-static const char *check_colouring(const examg_colouring_t *col, int nd, bool with_rem) {
-  if (col->nexpr < 1 || col->nexpr > 3) return "nexpr must be 1, 2 or 3";
-  for (int k = 0; k < col->nexpr; ++k) {
-    if (col->mod[k] <= 0) return "mod must be positive";
-    if (col->axes[k] <= 0 || col->axes[k] >= (1 << nd)) return "axes must name a non-empty set of the layout's axes";
-    if (with_rem && (col->rem[k] < 0 || col->rem[k] >= col->mod[k])) return "rem must lie in [0, mod)";
-  }
-  return nullptr;
-}
-
-static bool starts_nonnegative(const examg_colouring_t *col, const int32_t *begin) {
-  for (int k = 0; k < col->nexpr; ++k) {
-    long long s = col->shift[k];
-    for (int d = 0; d < 3; ++d)
-      if (col->axes[k] & (1 << d)) s += begin[d];
-    if (s < 0) return false;
-  }
-  return true;
-}
-
 static bool decouples(const examg_colouring_t *col, const examg_stencil_t *st) {
   for (int e = 0; e < st->nent; ++e) {
     const int32_t *o = st->off[e];
     if (o[0] == 0 && o[1] == 0 && o[2] == 0) continue;
-    bool apart = false;
-    for (int k = 0; k < col->nexpr; ++k) {
-      int s = 0;
-      for (int d = 0; d < 3; ++d)
-        if (col->axes[k] & (1 << d)) s += o[d];
-      apart = apart || (s % col->mod[k] != 0);
-    }
-    if (!apart) return false;
+    if (!colouring_separates(col, o)) return false;
   }
   return true;
 }
@@ -236,36 +179,8 @@ static int launch_coloured(int mode, const examg_layout_t *lu_, const double *u,
   const LayoutDev lc = fill_stencil_dev(sd, st, lu);
   sd.wdiv = st->wform == EXAMG_WEIGHT_DIVIDE ? 1 : 0;
 
-  MCColour c;
-  c.nexpr = col->nexpr;
-  for (int k = 0; k < 3; ++k) {
-    const bool on = k < col->nexpr;
-    c.axes[k] = on ? col->axes[k] : 0;
-    c.shift[k] = on ? col->shift[k] : 0;
-    c.mod[k] = on ? col->mod[k] : 1;
-    c.rem[k] = on ? col->rem[k] : 0;
-  }
-  const int bb[3] = {box.b0, box.b1, box.b2}, ee[3] = {box.e0, box.e1, box.e2};
-  for (int d = 0; d < 3; ++d) {
-    c.first[d] = bb[d];
-    c.step[d] = 1;
-    for (int k = 0; k < col->nexpr; ++k)
-      if (col->axes[k] == (1 << d) && c.step[d] == 1 && col->mod[k] > 1) {      // the first single-axis expression of the axis
-        const int n = col->mod[k];
-        c.step[d] = n;
-        c.first[d] = bb[d] + (col->rem[k] - (col->shift[k] + bb[d]) % n + n) % n;
-      }
-    c.count[d] = c.first[d] < ee[d] ? (ee[d] - c.first[d] + c.step[d] - 1) / c.step[d] : 0;
-  }
-  c.rowk = -1;
-  c.row_w = c.count[0];
-  if (c.step[0] == 1)
-    for (int k = 0; k < col->nexpr && c.rowk < 0; ++k)
-      if ((col->axes[k] & 1) && col->axes[k] != 1 && col->mod[k] > 1) {
-        c.rowk = k;
-        c.row_w = (box.n0() + col->mod[k] - 1) / col->mod[k];
-      }
-  const long long total = (long long)c.row_w * c.count[1] * c.count[2];
+  const MCColour c = make_colour(col, box);
+  const long long total = mc_threads(c);
   if (total == 0) return 0;      // no lattice point in the box
   long long nb = (total + 255) / 256;
   if (nb > 8192) nb = 8192;

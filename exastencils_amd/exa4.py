@@ -65,6 +65,7 @@ from .exa4_parser import (Exa4SyntaxError, Exa4Unsupported, FunctionDecl, Parser
                           _colour_cond, _colour_expr, _conjuncts, _const_value, _contains, _find_calls, _has_coord, _lower_cond, _parity_expr, _walk)
 
 from .exa4_systems import Systems  # noqa: E402
+from .exa4_blocksys import BlockSystems  # noqa: E402
 from .exa4_nonlinear import Nonlinear  # noqa: E402
 from .exa4_statements import Statements  # noqa: E402
 from .exa4_common import (APPLY, RESIDUAL, SMOOTH, _FN_2D_ONLY, _FN_ANY_DIM, _FN_WITH_PARAM, _N_FN, _Frame, _Return, fn_eval)  # noqa: E402,F401
@@ -75,7 +76,7 @@ from .exa4_conservation import Conservation, _EXPR, expand  # noqa: E402
 from .exa4_complex import ComplexFields  # noqa: E402
 
 
-class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonlinear, Conservation, ComplexFields):
+class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSystems, Nonlinear, Conservation, ComplexFields):
     """One ExaSlang-4 program bound to a kernel layer (`ops`: HipOps on the GPU), a block decomposition and a
     communicator.  `run()` executes `Function Application`; printed lines are collected in `self.out`."""
 
@@ -1160,6 +1161,10 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         if where is not None and any(_colour_cond(c, self.nd) is not None for c in _conjuncts(where)):
             raise Exa4Unsupported("`where` colour test in a loop under a multi-colouring (color with several expressions)")
         boxes, _ = self._loop_boxes(f, only, where, reduction, fr)
+        if any(st[0] == "solve" for st in body):      # the collective smoother of a block system (exa4_blocksys.py): one launch per colour
+            if len(body) != 1:
+                raise Exa4Unsupported("solve locally beside other statements, in a reduction or in an `only` loop")
+            return self._exec_solve_locally(body[0], boxes, None, fr, only, where)
         for st in body:
             if st[0] != "assign":
                 raise Exa4Unsupported("statement %r inside a loop body" % st[0])
@@ -1172,6 +1177,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             self._recognise_assign(st, fr)      # names what the loop assigns to
         if self._names_coef_expr(st[3]):
             raise Exa4Unsupported("semilinear operator (coefficient-expression stencil) %s" % what)
+        if st[1] == "=" and st[2][0] == "fld":
+            self._recognise_block_row(*self._field(st[2], fr), st[3], None, fr)      # a system row here is refused by name
         k = self._recognise_or_none(st, fr)     # whatever the recogniser refuses has no coloured kernel either
         if k is None or not self._launch_coloured(k, b, e, fr.mcolour):
             raise Exa4Unsupported("loop body statement %s %s ... %s: only stencil loops (A * u, f - A * u, u + w * (f - A * u)) have a coloured kernel"
@@ -1308,7 +1315,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
         if any(st[0] == "solve" for st in body):
             if len(body) != 1 or reduction is not None or only is not None:
                 raise Exa4Unsupported("solve locally beside other statements, in a reduction or in an `only` loop")
-            return self._exec_solve_locally(body[0], boxes, colour, fr)
+            return self._exec_solve_locally(body[0], boxes, colour, fr, only, where)
         if reduction is not None:
             return self._exec_reduction(f, boxes, reduction, body, fr)
         if body and all(st[0] == "assign" and st[2][0] == "sentry" for st in body):
@@ -1326,7 +1333,11 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
             return      # absorbed by a one-pass form later, or run when the next statement could tell the difference
         if (only is not None or fr.contract is not None) and self._names_coef_expr(("block", list(body))):
             raise Exa4Unsupported("semilinear operator in a loop with an `only` region or under contraction")
-        for st in body:
+        folded = 0
+        for i, st in enumerate(body):
+            if folded:      # a system row that went into the launch of the row before it (exa4_blocksys.py)
+                folded -= 1
+                continue
             if st[0] != "assign":
                 raise Exa4Unsupported("statement %r inside a loop body" % st[0])
             if only is not None and st[2][0] == "fld":      # boundary planes rewritten: second arrays of fused sweeps are stale
@@ -1337,6 +1348,9 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, Nonline
                 k = self._recognise_assign(st, fr, colour)
                 if self._is_lexicographic(k, colour):
                     self._check_lexicographic(k, only, where, fr)
+                if k.kind == "bsys_row":
+                    self._check_block_loop(only, where, fr)
+                    k, folded = self._merge_block_rows(k, body[i + 1:], fr)
                 self._launch(k, b, e, colour)
 
     def _exec_reduction(self, f: Field, boxes, reduction, body, fr: _Frame):

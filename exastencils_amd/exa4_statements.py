@@ -3,7 +3,7 @@ assignment stands for (`_recognise_assign` -> LoopStmt: a kind and the resolved 
 multi-colouring `_launch_coloured`).  Everyone who needs to know what a statement is switches on the record -- the loop executors of
 exa4.py, the smoother peepholes (exa4_peepholes.py: `_match_smoother`) and the pending loops of the cross-statement fusions
 (exa4_fusion.py: `_try_defer`, `_consume_residual`; a pending loop IS its record and is flushed through `_launch`).  System rows,
-point-wise set-up statements and semilinear operators are recognised in their mixins (exa4_systems.py, exa4_nonlinear.py), which hand
+point-wise set-up statements and semilinear operators are recognised in their mixins (exa4_systems.py, exa4_blocksys.py, exa4_nonlinear.py), which hand
 back a record and launch nothing.  Recognition raises before anything is counted; `launches` is the launcher's.  Whole-loop forms
 (reductions, stencil-field initialisation, rand / compare / check loops, `solve locally`) are not assignments of this kind and keep
 their own code.  tests/test_exa4_calls.py pins the calls that come out of all this."""
@@ -21,7 +21,7 @@ from .field import Field, Stencil
 class LoopStmt:
     """What one assignment in a loop body launches.  kind: set | fill_fn | fill_expr | fill_expr_cell | copy | axpby | add_scalar |
     residual | apply | smooth | restrict | restrict_cell | prolong_add | prolong_add_cell | sys_row | pointwise_mul | pointwise_sub |
-    nl_op | nl_smooth | axis_residual | axis_apply | axis_smooth | flux_step | reduce_expr | bc_face."""
+    bsys_row | nl_op | nl_smooth | axis_residual | axis_apply | axis_smooth | flux_step | reduce_expr | bc_face."""
     kind: str
     D: Field                        # the field assigned to
     ds: int
@@ -145,7 +145,8 @@ class Statements:
                 return LoopStmt("fill_fn", D, ds, prog=(fn, par)) if isinstance(fn, int) else LoopStmt("fill_expr", D, ds, prog=fn)
             if rhs[0] == "fld":
                 return LoopStmt("copy", D, ds, *self._field(rhs, fr), s=1.0, t=0.0)
-            k = self._recognise_system_row(D, ds, rhs, colour, fr) or (colour is None and self._recognise_pointwise(D, ds, rhs, fr))
+            k = (self._recognise_system_row(D, ds, rhs, colour, fr) or self._recognise_block_row(D, ds, rhs, colour, fr)
+                 or (colour is None and self._recognise_pointwise(D, ds, rhs, fr)))
             if k:
                 return k
             r = self._residual_form(rhs, fr)
@@ -262,6 +263,9 @@ class Statements:
         if kind == "reduce_expr":             # the device scalar goes back to the reduction loop, which reads it
             self.launches += 1
             return ops.reduce_expr_cell(int(k.s), D.lc, [X.data(s) for X, s in k.prog[0]], k.prog[1], b, e)
+        if kind == "bsys_row":              # (exa4_blocksys.py) the rows of a block system that stand together in a loop body
+            self.launches += 1
+            return self._launch_block_rows(k, b, e)
         if kind == "flux_step":
             ins, outs, spec = k.prog
             self.launches += 1

@@ -135,16 +135,20 @@ class Systems:
         return LoopStmt("sys_row", D, ds, F=FF, fs=fs, A=L, prog=(mode, us, terms[0][0], g, c))
 
     # -- solve locally --------------------------------------------------------------------------------------------------------
-    def _exec_solve_locally(self, st, boxes, colour, fr):
-        """`solve locally [relax w] { F_c => row_c == rhs_c .. }` in a coloured loop: one examg_sys_relax per box."""
+    def _exec_solve_locally(self, st, boxes, colour, fr, only=None, where=None):
+        """`solve locally [relax w] { F_c => row_c == rhs_c .. }` in a coloured loop: one examg_sys_relax per box.  Rows whose terms
+        are all constant stencils are a block system of node fields (exa4_blocksys.py: one examg_bsys_relax per box)."""
         _, jacobi, relax, rows = st
         if len(rows) == 1 and rows[0][0][0] == "fld" and self._field(rows[0][0], fr)[0].layout.is_complex:
             return self._exec_complex_solve(st, boxes, colour, fr)      # one complex node unknown: EXAMG_CRELAX (exa4_complex.py)
         if any(u[0] == "fld" and self._field(u, fr)[0].layout.is_complex for u, _, _ in rows):
             raise Exa4Unsupported("solve locally with more than one unknown over complex fields (the system path knows real cell fields)")
+        terms = self._block_solve_rows(rows)
+        if terms is not None:
+            return self._exec_block_solve(st, terms, boxes, colour, only, where, fr)
         if jacobi:
             raise Exa4Unsupported("solve locally with jacobi")
-        if colour is None:
+        if colour is None and fr.mcolour is None:
             raise Exa4Unsupported("solve locally in an uncoloured loop")
         if len(rows) > 3:
             raise Exa4Unsupported("solve locally with more unknowns than 3 (%d)" % len(rows))

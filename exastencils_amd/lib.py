@@ -72,6 +72,16 @@ class SysC(C.Structure):
                 ("f", C.c_void_p * SYS_MAX), ("g", C.c_void_p * (SYS_MAX * SYS_MAX)), ("dst", C.c_void_p * SYS_MAX)]
 
 
+BSYS_MAX = 3
+BSYS_GATHER = 1                           # what examg_bsys_route answers (-1 refused, 0 empty box)
+
+
+class BsysC(C.Structure):
+    """examg_bsys_t: the arrays and the n x n table of constant stencils of a coupled system of n = 2 or 3 node fields (include/examg.h)."""
+    _fields_ = [("n", C.c_int32), ("lu", LayoutC), ("lf", LayoutC), ("ld", LayoutC), ("u", C.c_void_p * BSYS_MAX), ("f", C.c_void_p * BSYS_MAX),
+                ("dst", C.c_void_p * BSYS_MAX), ("A", C.POINTER(StencilC) * (BSYS_MAX * BSYS_MAX))]
+
+
 MAX_EXPR = 256
 OPS = {"const": 0, "x": 1, "y": 2, "z": 3, "+": 4, "-": 5, "*": 6, "/": 7, "neg": 8, "sin": 9, "cos": 10, "exp": 11, "sinh": 12,
        "cosh": 13, "sqrt": 14, "pow": 15, "tan": 16, "log": 17, "fabs": 18, "max": 19, "min": 20, "tanh": 21}
@@ -183,6 +193,7 @@ SYMBOLS = [
     "examg_prolong_add_cell",
     "examg_stencil_op_coloured", "examg_mcgs_sweep", "examg_mcgs_one_pass_eligible",
     "examg_sys_op", "examg_sys_relax", "examg_pointwise_mul",
+    "examg_bsys_op", "examg_bsys_relax", "examg_bsys_route",
     "examg_nl_op", "examg_nl_smooth",
     "examg_gs_sweep", "examg_gs_route",
     "examg_axis_op", "examg_axis_route", "examg_fill_expr_grid", "examg_apply_dirichlet_expr_grid", "examg_max_err_expr_grid",
@@ -317,6 +328,10 @@ def load(path=None):
     L.examg_sys_op.argtypes = [C.c_int, yp, sp, C.c_uint32, ip, ip, vp]
     L.examg_sys_relax.argtypes = [yp, sp, C.c_double, C.c_int, ip, ip, vp]
     L.examg_pointwise_mul.argtypes = [lp, vp, lp, vp, lp, vp, C.c_double, ip, ip, vp]
+    bp = C.POINTER(BsysC)
+    L.examg_bsys_op.argtypes = [C.c_int, bp, C.c_uint32, ip, ip, vp]
+    L.examg_bsys_relax.argtypes = [bp, C.c_double, cp, ip, ip, vp]
+    L.examg_bsys_route.argtypes = [C.c_int, bp, C.c_uint32, ip, ip]
     np_ = C.POINTER(NlExprC)
     L.examg_nl_op.argtypes = [C.c_int, lp, vp, lp, vp, lp, vp, lp, vp, sp, np_, ip, ip, vp]
     L.examg_nl_smooth.argtypes = [lp, vp, lp, vp, lp, vp, sp, np_, np_, C.c_double, C.c_int, ip, ip, vp]

@@ -358,6 +358,55 @@ class HipOps:
         check(self.L.examg_pointwise_mul(C.byref(lx), self.ptr(x), C.byref(ly), self.ptr(y), C.byref(ld), self.ptr(dst), float(s), ivec(begin),
                                          ivec(end), self._stream()), "examg_pointwise_mul")
 
+    # -- coupled systems of node fields whose blocks are stencils --------------------------------------
+    def _bsys(self, lu, u, lf, f, A, ld=None, dst=None):
+        """examg_bsys_t of the unknowns u (layout lu), right-hand sides f (lf; None where not read), the n x n table A of constant
+        stencils (rows of n, None: no block; a block need not have a centre entry) and the destinations dst (ld).  The stencil
+        structs live as long as the returned struct (`keep`)."""
+        n = len(u)
+        y = _lib.BsysC()
+        y.n = n
+        for name, l in (("lu", lu), ("lf", lf if lf is not None else lu), ("ld", ld if ld is not None else lu)):
+            C.memmove(C.byref(getattr(y, name)), C.byref(l), C.sizeof(_lib.LayoutC))
+        m = min(n, _lib.BSYS_MAX)       # an n the library refuses still reaches it
+        y.keep = []
+        for c in range(m):
+            y.u[c] = self.ptr(u[c])
+            y.f[c] = self.ptr(f[c]) if f is not None and f[c] is not None else None
+            y.dst[c] = self.ptr(dst[c]) if dst is not None and dst[c] is not None else None
+            for d in range(m):
+                st = A[c][d]
+                if st is None:
+                    continue
+                sc = _lib.StencilC()
+                sc.nent = len(st.offsets)
+                sc.diag = st.offsets.index((0, 0, 0)) if (0, 0, 0) in st.offsets else 0      # (not looked at)
+                for k, o in enumerate(st.offsets[:_lib.MAXE]):
+                    for t in range(3):
+                        sc.off[k][t] = o[t]
+                    sc.coef[k] = st.coefs[k] if st.coefs else 0.0
+                if st.cfield is not None:
+                    sc.cfield = self.ptr(st.cfield)
+                    sc.clayout = st.clayout.c_struct()
+                y.keep.append(sc)
+                y.A[c * m + d] = C.pointer(sc)
+        return y
+
+    def bsys_op(self, mode: int, lu, u, lf, f, ld, dst, A, row_mask: int, begin, end):
+        """dst_c = sum_d A[c][d] * u_d (lib.SYS_APPLY) or f_c minus it (lib.SYS_RESIDUAL) for the rows of row_mask (examg_bsys_op)."""
+        y = self._bsys(lu, u, lf, f, A, ld, dst)
+        check(self.L.examg_bsys_op(int(mode), C.byref(y), int(row_mask), ivec(begin), ivec(end), self._stream()), "examg_bsys_op")
+
+    def bsys_relax(self, lu, u, lf, f, A, relax: float, col: Colouring, begin, end):
+        """The local solves of one colour of the collective point smoother of the block system A, in place on u (examg_bsys_relax)."""
+        y, cc = self._bsys(lu, u, lf, f, A), col.c_struct()
+        check(self.L.examg_bsys_relax(C.byref(y), float(relax), C.byref(cc), ivec(begin), ivec(end), self._stream()), "examg_bsys_relax")
+
+    def bsys_route(self, mode: int, lu, u, lf, f, ld, dst, A, row_mask: int, begin, end) -> int:
+        """What bsys_op does with these arguments: -1 refused (the reason in examg_last_error), 0 empty box, lib.BSYS_GATHER."""
+        y = self._bsys(lu, u, lf, f, A, ld, dst)
+        return int(self.L.examg_bsys_route(int(mode), C.byref(y), int(row_mask), ivec(begin), ivec(end)))
+
     # -- semilinear operators A * u + c(q) . u -------------------------------------------------------
     def nl_op(self, mode: int, lu, u, lq, q, lf, rhs, ld, dst, st: Stencil, c, begin, end):
         """dst = N (lib.NL_APPLY), rhs - N (lib.NL_RESIDUAL) or dst + N (lib.NL_ADD), N = st * u + c(q) . u; c: lib.NlExprC (examg_nl_op)."""

@@ -808,6 +808,81 @@ int examg_sys_relax(const examg_sys_t *sys, const examg_stencil_t *L, double rel
 int examg_pointwise_mul(const examg_layout_t *lx, const double *x, const examg_layout_t *ly, const double *y, const examg_layout_t *ld,
                         double *dst, double s, const int32_t *begin, const int32_t *end, examg_stream_t stream);
 
+/* ---- Coupled systems of node-centred unknowns whose blocks are stencils ------------------------------------------------------
+ * n = 2 or 3 scalar node fields u_0 .. u_{n-1} and an n x n table of constant stencils: row c of the operator is
+ *     Au_c = sum over d of A_cd * u_d
+ * (Examples/LinearElasticity/2D_FD_LinearElasticity_fromL2.exa2: `( lambda + mu ) * ( dxx * u + dxy * v ) + lambda * Laplace * u`,
+ * the displacement form of linear elasticity: the off-diagonal block dxy has four diagonal neighbours and no centre).
+ * examg_bsys_t names the arrays:
+ *   u[c]          the unknowns, all in layout lu
+ *   f[c]          the right-hand sides, all in layout lf
+ *   dst[c]        the destinations of examg_bsys_op, all in layout ld; no dst may be one of the unknowns, nor -- in EXAMG_SYS_RESIDUAL -- one
+ *                 of the right-hand sides (the rows are stored one after the other)
+ *   A[c * n + d]  the stencil that acts on u_d in row c; NULL: no such block.  A constant stencil (cfield NULL) with 1 .. 27 entries,
+ *                 offsets in {-1, 0, 1}^nd, in any order, each offset at most once; a block need not have a centre entry.  The order
+ *                 of the entries is significant; `diag` is not looked at.
+ * Entries of the arrays behind n are ignored.  The three layouts are plain layouts (no layout transformation) of node fields (not
+ * cell layouts: inner + duplicate points per axis count) of one dimensionality (2 or 3) with the same inner sizes and duplicate
+ * layers; ghost and pad widths may differ.
+ * STENCIL ARITHMETIC is the host's business, as for examg_sys_op: a scalar factor in front of a stencil, evaluated left to right as
+ * written, multiplies every coefficient; two stencils on one unknown (`( lambda + mu ) * dxx` and `lambda * Laplace` on u) are added
+ * into one block in order of appearance -- an offset already present gets c_old + c_new, a new offset is appended.
+ *
+ * Arithmetic, fp64, no contraction.  conv(S, x) = the entries of S folded left to right in declared order: c_0 * x(i + o_0), then
+ * + c_k * x(i + o_k) (stencil/ir/IR_StencilConvolution.scala:65-68).
+ *   row value    Au_c = (conv(A_c0, u_0) + conv(A_c1, u_1)) [+ conv(A_c2, u_2)]: the blocks left to right in d; NULL blocks are
+ *                skipped, not multiplied by zero.  A row of the call without any block is an error.
+ *
+ * examg_bsys_op: for every row c of row_mask (bit c) and every point of [begin,end)
+ *   EXAMG_SYS_APPLY:    dst_c = Au_c
+ *   EXAMG_SYS_RESIDUAL: dst_c = f_c - Au_c
+ * Rows outside the mask are neither evaluated nor written.  Reads the unknowns on the box and its one-point shell, diagonal
+ * neighbours included, right-hand sides on the box; writes the box of dst_c and nothing else.
+ *
+ * examg_bsys_relax: one colour of the collective point smoother, in place --
+ *     `color with { .., loop over u { solve locally relax w { u => rowU == rhs_u   v => rowV == rhs_v } } }`
+ * (solver/l4/L4_LocalSolve.scala, solver/ir/IR_LocalSolve.scala: the unknowns at the loop's point form AVals, every other term goes
+ * to fVals).  For every point of [begin,end) that belongs to the colour `col` (examg_colouring_t above: every e_k == rem[k])
+ *   a_cd = the centre coefficient of A_cd, 0.0 for a NULL block or a block without a centre entry
+ *   b_c  = f_c - (off-centre part of row c);  the off-centre part: the entries of A_cd off the centre folded left to right in declared
+ *          order over u_d, for each d in order, the per-block sums added left to right; blocks without an off-centre entry are skipped;
+ *          b_c = f_c when no block of the row has one
+ *   x solves a x = b with the n = 2 and n = 3 formulas of examg_sys_relax above (det; the cofactors each a difference of two products)
+ *   u_c = u_c + relax * (x_c - u_c);  relax == 1.0: u_c = x_c, no arithmetic
+ * Reads the neighbours and the point's own values; writes the colour's points of the box in the u_c and nothing else.  The loop is
+ * independent of its order only when no neighbour that a point reads belongs to its own colour: the colouring must DECOUPLE (see
+ * examg_colouring_t) the union of the off-centre offsets of all blocks.  The parity of all indices does not decouple dxy, whose four
+ * diagonal neighbours have the point's own colour; `i0 % 2, i1 % 2 [, i2 % 2]` decouples every block of reach 1.
+ *
+ * Both refuse, before anything is launched: n outside 2 .. 3; a cell layout, a layout under a layout transformation or one that is
+ * not 2-D or 3-D; layouts of different inner sizes or dimensionality; a stencil field as a block; an entry that reaches further than
+ * one point (or off the layout's axes); a repeated offset; a row (of the mask) without blocks; a dst that is one of the unknowns or of the right-hand sides read; a
+ * box whose one-point shell leaves the allocation of the unknowns, or that leaves the allocation of f or dst.  examg_bsys_relax also
+ * refuses a zero a_cc in the input (det is not checked), a colouring that does not decouple the blocks, and what the coloured entry
+ * points refuse of a colouring (nexpr, mod, rem, axes, a colour expression that can be negative in the box).  An empty box is a no-op
+ * that returns 0.
+ *
+ * One kernel per entry point, a lane owns four points (of the colour) in consecutive rows: every row of the call is evaluated in one
+ * pass, the neighbourhood of an unknown that several rows read comes from memory once and from the vector L1 afterwards (24 * n
+ * compulsory bytes per point for a full residual).  The stencils travel as kernel arguments: no allocation, no scratch, no host
+ * synchronisation; capturable.  A plane of the unknowns' layout has fewer than 2^31 points (32-bit neighbour offsets; refused otherwise).
+ * examg_bsys_route: what examg_bsys_op does with these arguments: -1 refused (the reason in examg_last_error), 0 empty box,
+ * EXAMG_BSYS_GATHER -- the one route: a marching kernel was measured against it and lost at every size. */
+#define EXAMG_BSYS_MAX 3
+enum { EXAMG_BSYS_GATHER = 1 };
+typedef struct examg_bsys {
+  int32_t n;
+  examg_layout_t lu, lf, ld;
+  double *u[EXAMG_BSYS_MAX];
+  const double *f[EXAMG_BSYS_MAX];
+  double *dst[EXAMG_BSYS_MAX];
+  const examg_stencil_t *A[EXAMG_BSYS_MAX * EXAMG_BSYS_MAX];
+} examg_bsys_t;
+int examg_bsys_op(int mode, const examg_bsys_t *sys, uint32_t row_mask, const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_bsys_relax(const examg_bsys_t *sys, double relax, const examg_colouring_t *col, const int32_t *begin, const int32_t *end,
+                     examg_stream_t stream);
+int examg_bsys_route(int mode, const examg_bsys_t *sys, uint32_t row_mask, const int32_t *begin, const int32_t *end);
+
 /* ---- Semilinear operators: N(q; u) = A * u + c(q) . u ---------------------------------------------------------------------
  * A a constant stencil (cfield NULL; any entry list, 2-D or 3-D), c a point expression over the value of a node field q AT THE POINT:
  * `Stencil gamSten { [0, 0] => gam * exp ( Solution<active>@current ) }`, `Laplace * Solution + gamSten * Solution`

@@ -17,7 +17,9 @@
 // Arithmetic per point is the same expression, in the same order, as the one-stage kernels: results are
 // bit-identical to running the two loops one after the other.
 #include "examg_common.h"
+#include "ts3_plan.h"
 
+#include <atomic>
 #include <type_traits>
 
 namespace examg {
@@ -746,10 +748,10 @@ constexpr int TS3_OUT = 120;   // outputs per 128-point window: lanes 2 .. 61
 // colour g.first again (three sweeps = six colour loops = two such passes, the second one starting with the other colour).  Which point of a
 // pair a stage updates is the same for all three stages of a step (plane and colour both move by one from stage to stage) and wave-uniform
 // per row: one convolution per pair and stage, the other point passes through.
-template <int ORDER, int NW, bool NT, int RPW = 3, bool COL = false, bool FMA = false>
+template <int ORDER, int NW, bool NT, int RPW = 3, bool COL = false, bool FMA = false, bool PLAN = false>
 __global__ void __launch_bounds__(64 * NW, 1)
 k_three_stage7_lds(LayoutDev lu, const double *__restrict__ u, LayoutDev lf, const double *__restrict__ rhs,
-                   double *__restrict__ out, Coef7 k, double w, Box box, TSGeom g) {
+                   double *__restrict__ out, Coef7 k, double w, Box box, TSGeom g, TS3Plan pl) {
   constexpr int NS = RPW * NW;      // stage-1 rows s = 0 .. NS-1, global row rw0 - 2 + s
   constexpr int NO = NS - 4;        // output rows: s = 2 .. NS-3
   // edge rows of the waves, two plane buffers each: [wave][field][buffer][lo / hi][lane] -- a wave's twelve rows lie within 12 KB, so one
@@ -765,22 +767,44 @@ k_three_stage7_lds(LayoutDev lu, const double *__restrict__ u, LayoutDev lf, con
     return reinterpret_cast<d2 *>(reinterpret_cast<char *>(SM) + off + threadIdx.x * 16u);
   };
   const int lane = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(threadIdx.y);
-  int t = blockIdx.x;
-  if (g.remap == 2) {  // XCD-contiguous within every z layer of tiles (see k_two_stage7_lds)
-    const int xy = g.ntx * g.nty;
-    const int lz = t / xy, r = t - lz * xy;
-    const int per = xy >> 3;
-    t = lz * xy + (r < (per << 3) ? (r & 7) * per + (r >> 3) : r);
+  // block -> tile column and z chunk, all of it wave-uniform.  PLAN: through the launch plan (ts3_plan.h) -- segment (unused segments start
+  // past the last block), position in the segment's block order, layer.  Otherwise the uniform grid g.ntx x g.nty x g.ntz of chunks of g.zc
+  // planes, which is what a one-segment plan in natural order describes: those launches keep the decode (and the code) they always had.
+  int t = blockIdx.x, tx, ty, mb, me;
+  if constexpr (PLAN) {
+    TS3Seg sg = pl.seg[0];
+    if (t >= pl.seg[1].first) sg = pl.seg[1];
+    if (t >= pl.seg[2].first) sg = pl.seg[2];
+    t -= sg.first;
+    const int pos = t / sg.ncol;
+    int col = t - pos * sg.ncol;
+    if (g.remap == 2) {  // XCD-contiguous within every layer of the segment (see k_two_stage7_lds)
+      const int per = sg.ncol >> 3;
+      col = col < (per << 3) ? (col & 7) * per + (col >> 3) : col;
+    }
+    col += sg.col0;
+    const int tz = sg.order == TS3_INTERLEAVED ? ((pos & 1) ? ((sg.nl + 1) >> 1) + (pos >> 1) : (pos >> 1)) : pos;
+    ty = col / g.ntx;
+    tx = col - ty * g.ntx;
+    mb = box.b2 + sg.z0 + tz * sg.zc;           // first output plane
+    me = min(mb + sg.zc, box.b2 + sg.z1);
+  } else {
+    if (g.remap == 2) {  // XCD-contiguous within every z layer of tiles (see k_two_stage7_lds)
+      const int xy = g.ntx * g.nty;
+      const int lz = t / xy, r = t - lz * xy;
+      const int per = xy >> 3;
+      t = lz * xy + (r < (per << 3) ? (r & 7) * per + (r >> 3) : r);
+    }
+    tx = t % g.ntx;
+    t /= g.ntx;
+    ty = t % g.nty;
+    const int tz = t / g.nty;
+    mb = box.b2 + tz * g.zc;                    // first output plane
+    me = min(mb + g.zc, box.e2);
   }
-  const int tx = t % g.ntx;
-  t /= g.ntx;
-  const int ty = t % g.nty;
-  const int tz = t / g.nty;
   const int xw = box.b0 - 4 + TS3_OUT * tx;     // first point of the window
   const int xa = xw + 2 * lane;
   const int rw0 = box.b1 + ty * NO;             // first output row of the workgroup
-  const int mb = box.b2 + tz * g.zc;            // first output plane
-  const int me = min(mb + g.zc, box.e2);
   const bool inx_a = xa >= box.b0 && xa < box.e0, inx_b = xa + 1 >= box.b0 && xa + 1 < box.e0;
   const bool out_lane = lane >= 2 && lane <= 61;
   const bool st_a = out_lane && inx_a, st_b = out_lane && inx_b;
@@ -1028,6 +1052,31 @@ k_three_stage7_lds(LayoutDev lu, const double *__restrict__ u, LayoutDev lf, con
 
 static thread_local int g_ts3_zc = -1;         // planes per z chunk of the three-step pass; -1: by size (examg_debug_three_stage)
 static thread_local int g_ts3_disable = 0;
+// examg_debug_three_stage_plan: the whole-round plan forced -- layers per round, rounds, layer order, assumed CU count (<= 0 / < 0: by the rule)
+static thread_local int g_ts3_m = 0, g_ts3_rounds = 0, g_ts3_order = -1, g_ts3_cus = 0;
+// Whole rounds of the CUs (ts3_plan.h) for the fused form from 10^8 points on: the longest main chunk the planner may choose, and the layer
+// order of the main segment (0 would keep the uniform grid everywhere).  tools/time_three_stage_plans.py, MI355X, 512^3 (130 columns: 128 in
+// the main segment), ms per pass and fabric-side GB: the uniform rule (28 planes) 0.650 / 4.28; 2 x 8 layers of 32 planes 0.642 / 4.08 (interleaved
+// 0.650); 2 x 6 0.641 / 4.01 (0.637); 2 x 4 of 64 planes 0.631 / 3.93 (0.628); 2 x 2 of 128 0.615 / 3.81 (0.617); 2 x 1 of 256 planes
+// 0.613 / 3.72 -- the y neighbours stay in step over 256 planes (the traffic is what the tile model gives), so the longest chunks win and
+// the layer order has nothing to decide.  The colour form, same tool with --colour: rule (48 planes) 0.711, 2 x 4 0.666-0.672, 2 x 2 0.650-0.652,
+// 2 x 1 0.639-0.649.  256^3 (39 columns, 7 layers per round), Jacobi: rule 0.090, 7 x 1 0.097, 7 x 2 0.099-0.102: boxes below 10^8 points
+// keep the uniform grid, and so does the form with separate products, which was not measured.
+constexpr int TS3_ROUNDS_CMAX = 256;
+constexpr int TS3_ROUNDS_ORDER = TS3_NATURAL;
+
+// CUs of the current device, asked once per device: one workgroup of the three-step pass per CU
+static int device_cus() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  int n = cus[dev].load(std::memory_order_relaxed);
+  if (n <= 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
 static thread_local long long g_ts3_minpts = 8000000LL;      // examg_debug_three_stage(2, ..): 2^20, so that the parity tests reach the kernel on small boxes
 
 // the three-stage pass: 3-D 7-point constant stencils on rows of at least 64 points and at least 8 * 10^6 points -- below, a pass per pair of
@@ -1061,22 +1110,20 @@ static int launch_three_stage_shape(const examg_layout_t *lu_, const double *u, 
   // instead of 16 fp64 instructions per update.  The Jacobi form only: the colour form spills 28 bytes with them (0.71 -> 0.83 ms at 512^3).
   const bool fma = !COL && !g_pow2_fma_off && pow2_offdiag7(st);
   const int cmax = (fma && box.count() >= 100000000LL) ? 28 : 64;
-  int zc = n2;
-  {
-    long long best = -1;
-    for (int t = 1; t <= (n2 + 7) / 8; ++t) {
-      const int c = (n2 + t - 1) / t, tt = (n2 + c - 1) / c;
-      if ((c > cmax && t < (n2 + 7) / 8) || (c < 16 && t > 1)) continue;
-      const long long cost = (((long long)xy * tt + 255) / 256) * (((c + 4 + 3) & ~3) + 4);      // whole groups of four steps
-      if (best < 0 || cost < best) { best = cost; zc = c; }
-    }
-    if (zc + 3 < n2) zc = (zc + 3) & ~3;       // zc + 4 steps: a multiple of four wastes none
-  }
-  if (g_ts3_zc > 0) zc = g_ts3_zc;
-  if (zc > n2) zc = n2;
-  g.zc = zc;
-  g.ntz = (n2 + zc - 1) / zc;
-  g.nblocks = xy * g.ntz;
+  // the launch plan (ts3_plan.h): the uniform grid of that rule, or whole rounds of the CUs where the fused form has them (TS3_ROUNDS_CMAX)
+  TS3Rule rule;
+  rule.P = g_ts3_cus > 0 ? g_ts3_cus : device_cus();
+  rule.cmax = cmax;
+  rule.rounds_cmax = ((fma || COL) && box.count() >= 100000000LL) ? TS3_ROUNDS_CMAX : 0;
+  rule.order = g_ts3_order >= 0 ? g_ts3_order : TS3_ROUNDS_ORDER;
+  rule.force_zc = g_ts3_zc;
+  rule.force_m = g_ts3_m;
+  rule.force_rounds = g_ts3_rounds;
+  const TS3Plan pl = ts3_plan(xy, n2, rule);
+  g.zc = pl.seg[0].zc;
+  g.ntz = pl.seg[0].nl;
+  g.nblocks = pl.nblocks;
+  const bool planned = pl.nseg > 1 || pl.seg[0].order != TS3_NATURAL;      // else: the uniform grid, decoded from g as ever
   g.remap = g_ts_remap >= 0 ? g_ts_remap : 2;
   g.first = first;
   g.box1 = box;
@@ -1090,7 +1137,10 @@ static int launch_three_stage_shape(const examg_layout_t *lu_, const double *u, 
   with_order(ord, [&](auto O) {
     constexpr int ORD = decltype(O)::value;
     auto go = [&](auto NTc, auto Fc) {
-      hipLaunchKernelGGL((k_three_stage7_lds<ORD, NW, decltype(NTc)::value, RPW, COL, decltype(Fc)::value>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g);
+      if (planned)
+        hipLaunchKernelGGL((k_three_stage7_lds<ORD, NW, decltype(NTc)::value, RPW, COL, decltype(Fc)::value, true>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g, pl);
+      else
+        hipLaunchKernelGGL((k_three_stage7_lds<ORD, NW, decltype(NTc)::value, RPW, COL, decltype(Fc)::value, false>), grid, block, 0, s, lu, u, lf, rhs, out, k, w, box, g, pl);
     };
     if constexpr (!COL) {
       if (fma) return nt ? go(std::true_type{}, std::true_type{}) : go(std::false_type{}, std::true_type{});
@@ -1138,6 +1188,17 @@ extern "C" int examg_debug_three_stage(int disable, int zc) {
   g_ts3_disable = disable == 1;
   g_ts3_minpts = disable == 2 ? (1LL << 20) : 8000000LL;
   g_ts3_zc = zc > 0 ? zc : -1;
+  return 0;
+}
+
+// the whole-round plan of the three-step pass forced: m layers per round, that many rounds, layer order (0 natural, 1 interleaved halves) and
+// the CU count the planner assumes; <= 0 (order: < 0) leaves a figure to the rule, all four so the plan.  A forced chunk length
+// (examg_debug_three_stage) goes first.
+extern "C" int examg_debug_three_stage_plan(int layers_per_round, int rounds, int order, int cus) {
+  g_ts3_m = layers_per_round > 0 ? layers_per_round : 0;
+  g_ts3_rounds = rounds > 0 ? rounds : 0;
+  g_ts3_order = order < 0 ? -1 : (order ? TS3_INTERLEAVED : TS3_NATURAL);
+  g_ts3_cus = cus > 0 ? cus : 0;
   return 0;
 }
 

@@ -110,6 +110,21 @@ static inline bool box_inside(const examg_layout_t *l, const Box &b, int halo) {
 void set_error(const char *fmt, ...);
 int check_hip(hipError_t e, const char *what);
 
+// What every examg_vec_* entry point asks of its component count and of each layout of a vector-valued cell field (lb may be null):
+// n = 2 or 3, no duplicate layers, no layout transformation.  false: error text set.
+static inline bool vec_fields_ok(const char *who, int n, const examg_layout_t *la, const examg_layout_t *lb) {
+  if (n < 2 || n > EXAMG_VEC_MAX) { set_error("%s: n = %d components; vector-valued fields have 2 or 3", who, n); return false; }
+  const examg_layout_t *ls[2] = {la, lb};
+  for (int k = 0; k < 2; ++k) {
+    const examg_layout_t *l = ls[k];
+    if (!l) continue;
+    for (int d = 0; d < l->nd && d < 3; ++d)
+      if (l->dup_l[d] != 0 || l->dup_r[d] != 0) { set_error("%s: a cell layout has no duplicate layers (dim %d has %d / %d)", who, d, l->dup_l[d], l->dup_r[d]); return false; }
+    if (lay_split(l)) { set_error("%s: vector-valued fields under a layout transformation are not supported", who); return false; }
+  }
+  return true;
+}
+
 // one-pass kernels of the launch-bound levels (kernels_small.hip), tried by the entry points when the large-level kernels decline
 bool small_two_stage_ok(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const Box &box);
 int launch_small_two_stage(bool col, int var, const examg_layout_t *lu, const double *u_in, double *u_out, const examg_layout_t *lf, const double *rhs,

@@ -44,7 +44,9 @@ __device__ __forceinline__ void unflatten(const Box &box, long long t, int &i0, 
   i2 = box.b2 + (int)(row / n1);
 }
 
-__global__ void __launch_bounds__(256) k_set(LayoutDev l, double *x, double v, Box box) {
+// cs: doubles between the components of a vector-valued field; blockIdx.y is the component (a scalar field: one, cs unused)
+__global__ void __launch_bounds__(256) k_set(LayoutDev l, double *x, double v, Box box, long long cs) {
+  x += blockIdx.y * cs;
   const long long total = box.count();
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     int i0, i1, i2;
@@ -68,7 +70,9 @@ __global__ void __launch_bounds__(256) k_add_scalar(LayoutDev l, double *x, doub
 template <int DEV>
 __global__ void __launch_bounds__(256)
 k_axpby(LayoutDev lx, const double *x, LayoutDev ly, double *y, double a, double b, int form, double sign,
-        const double *num, const double *den, Box box) {
+        const double *num, const double *den, Box box, long long csx, long long csy) {
+  x += blockIdx.y * csx;     // the component of a vector-valued field (k_set)
+  y += blockIdx.y * csy;
   if (DEV == 1) a = sign * (*num / *den);
   if (DEV == 2) b = *num / *den;
   const long long total = box.count();
@@ -120,16 +124,27 @@ __device__ __forceinline__ double block_reduce(double v) {
   return r;  // valid in thread 0
 }
 
-// SUM: the terms are x alone (examg_sum; y is not read), else x * y
-template <bool SUM = false>
+// the term of one cell of vector-valued fields of NC components csx / csy doubles apart (examg_vec_dot): ((x_0 * y_0) + (x_1 * y_1)) [+ (x_2 * y_2)]
+template <int NC>
+__device__ __forceinline__ double vdot_term(const double *__restrict__ px, const double *__restrict__ py, long long csx, long long csy) {
+  double t = px[0] * py[0];
+#pragma unroll
+  for (int c = 1; c < NC; ++c) t = t + px[c * csx] * py[c * csy];
+  return t;
+}
+
+// SUM: the terms are x alone (examg_sum; y is not read), else x * y; NC > 1: the terms of vector-valued fields (vdot_term)
+template <bool SUM = false, int NC = 1>
 __global__ void __launch_bounds__(RED_BLOCK)
-k_dot_partial(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const double *__restrict__ y, Box box, double *part) {
+k_dot_partial(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const double *__restrict__ y, Box box, double *part, long long csx = 0,
+              long long csy = 0) {
   const long long total = box.count();
   double s = 0.0;
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     int i0, i1, i2;
     unflatten(box, t, i0, i1, i2);
     if (SUM) s = s + x[lidx(lx, i0, i1, i2)];
+    else if (NC > 1) s = s + vdot_term<NC>(x + lidx(lx, i0, i1, i2), y + lidx(ly, i0, i1, i2), csx, csy);
     else s = s + x[lidx(lx, i0, i1, i2)] * y[lidx(ly, i0, i1, i2)];
   }
   const double r = block_reduce<false>(s);
@@ -138,9 +153,10 @@ k_dot_partial(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const do
 
 // Long rows: a wave streams whole rows, two points per lane with 16-byte loads, no index divisions per element; the rows a
 // wave takes and the order it adds them in depend only on the launch geometry, so the sum is reproducible run to run.
-template <bool SUM = false>
+template <bool SUM = false, int NC = 1>
 __global__ void __launch_bounds__(RED_BLOCK)
-k_dot_rows(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const double *__restrict__ y, Box box, double *part) {
+k_dot_rows(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const double *__restrict__ y, Box box, double *part, long long csx = 0,
+           long long csy = 0) {
   const int lane = threadIdx.x & 63;
   const int n1 = box.n1();
   const long long nrows = (long long)n1 * box.n2();
@@ -159,6 +175,10 @@ k_dot_rows(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const doubl
         } else {
           s = s + px[i0];
         }
+      } else if (NC > 1) {
+        // the two cells of the lane one after the other, as the scalar form adds them
+        s = s + vdot_term<NC>(px + i0, py + i0, csx, csy);
+        if (i0 + 1 < box.e0) s = s + vdot_term<NC>(px + i0 + 1, py + i0 + 1, csx, csy);
       } else if (i0 + 1 < box.e0) {
         const d2 a = load2(px + i0), b = load2(py + i0);
         s = s + a.x * b.x;
@@ -314,14 +334,29 @@ extern "C" int examg_set(const examg_layout_t *l_, double *x, double v, const in
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   if (!box_inside(l_, box, 0)) { set_error("examg_set: box leaves the allocation"); return 1; }
-  hipLaunchKernelGGL(k_set, grid_for(box.count()), dim3(256), 0, (hipStream_t)stream, make_layout(l_), x, v, box);
+  hipLaunchKernelGGL(k_set, grid_for(box.count()), dim3(256), 0, (hipStream_t)stream, make_layout(l_), x, v, box, 0LL);
   EXAMG_CHECK_LAUNCH("k_set");
   return 0;
 }
 
+extern "C" int examg_vec_set(int n, const examg_layout_t *l_, double *x, double v, const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  if (!l_ || !x || !begin || !end) { set_error("examg_vec_set: null argument"); return 1; }
+  if (!vec_fields_ok("examg_vec_set", n, l_, nullptr)) return 1;
+  const Box box = make_box(begin, end);
+  if (box.count() == 0) return 0;
+  if (!box_inside(l_, box, 0)) { set_error("examg_vec_set: box leaves the allocation"); return 1; }
+  dim3 grid = grid_for(box.count());
+  grid.y = n;
+  const LayoutDev l = make_layout(l_);
+  hipLaunchKernelGGL(k_set, grid, dim3(256), 0, (hipStream_t)stream, l, x, v, box, l.size);
+  EXAMG_CHECK_LAUNCH("k_set");
+  return 0;
+}
+
+// ncomp > 1: every component of vector-valued fields (examg_vec_axpby), the component the y dimension of the grid
 static int axpby_impl(const examg_layout_t *lx_, const double *x, const examg_layout_t *ly_, double *y, double a, double b,
                       int dev, double sign, const double *num, const double *den, const int32_t *begin,
-                      const int32_t *end, examg_stream_t stream) {
+                      const int32_t *end, examg_stream_t stream, int ncomp = 1) {
   if (!lx_ || !x || !ly_ || !y || !begin || !end) { set_error("examg_axpby: null argument"); return 1; }
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
@@ -335,9 +370,12 @@ static int axpby_impl(const examg_layout_t *lx_, const double *x, const examg_la
   else form = 4;
   const LayoutDev lx = make_layout(lx_), ly = make_layout(ly_);
   hipStream_t s = (hipStream_t)stream;
-  if (dev == 0) hipLaunchKernelGGL((k_axpby<0>), grid_for(box.count()), dim3(256), 0, s, lx, x, ly, y, a, b, form, sign, num, den, box);
-  else if (dev == 1) hipLaunchKernelGGL((k_axpby<1>), grid_for(box.count()), dim3(256), 0, s, lx, x, ly, y, a, b, form, sign, num, den, box);
-  else hipLaunchKernelGGL((k_axpby<2>), grid_for(box.count()), dim3(256), 0, s, lx, x, ly, y, a, b, form, sign, num, den, box);
+  dim3 grid = grid_for(box.count());
+  grid.y = ncomp;
+  const long long csx = ncomp > 1 ? lx.size : 0, csy = ncomp > 1 ? ly.size : 0;
+  if (dev == 0) hipLaunchKernelGGL((k_axpby<0>), grid, dim3(256), 0, s, lx, x, ly, y, a, b, form, sign, num, den, box, csx, csy);
+  else if (dev == 1) hipLaunchKernelGGL((k_axpby<1>), grid, dim3(256), 0, s, lx, x, ly, y, a, b, form, sign, num, den, box, csx, csy);
+  else hipLaunchKernelGGL((k_axpby<2>), grid, dim3(256), 0, s, lx, x, ly, y, a, b, form, sign, num, den, box, csx, csy);
   EXAMG_CHECK_LAUNCH("k_axpby");
   return 0;
 }
@@ -345,6 +383,13 @@ static int axpby_impl(const examg_layout_t *lx_, const double *x, const examg_la
 extern "C" int examg_axpby(const examg_layout_t *lx, const double *x, const examg_layout_t *ly, double *y, double a,
                            double b, const int32_t *begin, const int32_t *end, examg_stream_t stream) {
   return axpby_impl(lx, x, ly, y, a, b, 0, 1.0, nullptr, nullptr, begin, end, stream);
+}
+
+extern "C" int examg_vec_axpby(int n, const examg_layout_t *lx, const double *x, const examg_layout_t *ly, double *y, double a, double b,
+                               const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  if (!lx || !x || !ly || !y || !begin || !end) { set_error("examg_vec_axpby: null argument"); return 1; }
+  if (!vec_fields_ok("examg_vec_axpby", n, lx, ly)) return 1;
+  return axpby_impl(lx, x, ly, y, a, b, 0, 1.0, nullptr, nullptr, begin, end, stream, n);
 }
 
 extern "C" int examg_axpby_dev(const examg_layout_t *lx, const double *x, const examg_layout_t *ly, double *y, double a,
@@ -389,6 +434,33 @@ extern "C" int examg_dot(const examg_layout_t *lx_, const double *x, const examg
     hipLaunchKernelGGL(k_dot_partial<false>, dim3(nb), dim3(RED_BLOCK), 0, s, make_layout(lx_), x, make_layout(ly_), y, box, (double *)work);
   hipLaunchKernelGGL((k_reduce_final<false>), dim3(1), dim3(RED_BLOCK), 0, s, (const double *)work, nb, result);
   EXAMG_CHECK_LAUNCH("k_dot");
+  return 0;
+}
+
+// examg_dot's launch plan, kernels and reduction tree with the per-cell terms of vector-valued fields
+template <int NC>
+static void vec_dot_launch(const examg_layout_t *lx_, const double *x, const examg_layout_t *ly_, const double *y, const Box &box, int nb, double *work,
+                           hipStream_t s) {
+  const LayoutDev lx = make_layout(lx_), ly = make_layout(ly_);
+  if (box.n0() >= 128)
+    hipLaunchKernelGGL((k_dot_rows<false, NC>), dim3(nb), dim3(RED_BLOCK), 0, s, lx, x, ly, y, box, work, lx.size, ly.size);
+  else
+    hipLaunchKernelGGL((k_dot_partial<false, NC>), dim3(nb), dim3(RED_BLOCK), 0, s, lx, x, ly, y, box, work, lx.size, ly.size);
+}
+
+extern "C" int examg_vec_dot(int n, const examg_layout_t *lx_, const double *x, const examg_layout_t *ly_, const double *y, const int32_t *begin,
+                             const int32_t *end, double *result, void *work, examg_stream_t stream) {
+  if (!lx_ || !x || !ly_ || !y || !begin || !end || !result || !work) { set_error("examg_vec_dot: null argument"); return 1; }
+  if (!vec_fields_ok("examg_vec_dot", n, lx_, ly_)) return 1;
+  const Box box = make_box(begin, end);
+  hipStream_t s = (hipStream_t)stream;
+  if (box.count() == 0) return check_hip(hipMemsetAsync(result, 0, sizeof(double), s), "examg_vec_dot memset");
+  if (!box_inside(lx_, box, 0) || !box_inside(ly_, box, 0)) { set_error("examg_vec_dot: box leaves an allocation"); return 1; }
+  const int nb = red_blocks(box.count());
+  if (n == 2) vec_dot_launch<2>(lx_, x, ly_, y, box, nb, (double *)work, s);
+  else vec_dot_launch<3>(lx_, x, ly_, y, box, nb, (double *)work, s);
+  hipLaunchKernelGGL((k_reduce_final<false>), dim3(1), dim3(RED_BLOCK), 0, s, (const double *)work, nb, result);
+  EXAMG_CHECK_LAUNCH("k_vec_dot");
   return 0;
 }
 

@@ -23,8 +23,10 @@ struct CellFaces {
 };
 
 // One launch for every face of the mask.  Thread t -> (face, boundary cell); the ghost is the cell one step outwards.
+// cs: doubles between the components of a vector-valued field, blockIdx.y the component (a scalar field: one) -- in all three kernels.
 template <int KIND>
-__global__ void __launch_bounds__(256) k_apply_bc_cell(LayoutDev l, double *x, Geom g, ExprEval fn, CellFaces fc, int3 inner) {
+__global__ void __launch_bounds__(256) k_apply_bc_cell(LayoutDev l, double *x, Geom g, ExprEval fn, CellFaces fc, int3 inner, long long cs) {
+  x += blockIdx.y * cs;
   const long long total = fc.start[fc.n];
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     int f = 0;
@@ -64,7 +66,10 @@ __global__ void __launch_bounds__(256) k_apply_bc_cell(LayoutDev l, double *x, G
 // VEC: the pair (2I, 2I+1) of every fine row with one aligned 16-byte load.
 template <int ND, bool VEC>
 __global__ void __launch_bounds__(256)
-k_restrict_cell(LayoutDev lf, const double *__restrict__ rf, LayoutDev lc, double *__restrict__ fc, double wgt, Box box, int ntx, int nwaves) {
+k_restrict_cell(LayoutDev lf, const double *__restrict__ rf, LayoutDev lc, double *__restrict__ fc, double wgt, Box box, int ntx, int nwaves,
+                long long csf, long long csc) {
+  rf += blockIdx.y * csf;
+  fc += blockIdx.y * csc;
   const int lane = threadIdx.x;
   const long long wg = xcd_band(blockIdx.x, ntx * ((box.n1() + 3) >> 2));
   const int wpl = ntx * ((box.n1() + 3) >> 2);
@@ -111,7 +116,9 @@ k_restrict_cell(LayoutDev lf, const double *__restrict__ rf, LayoutDev lc, doubl
 template <int ND, bool VEC>
 __global__ void __launch_bounds__(256)
 k_prolong_add_cell(LayoutDev lc, const double *__restrict__ uc, LayoutDev lf, double *__restrict__ uf, Box box, int cb0, int cb1, int cb2,
-                   int nc0, int nc1, int ntx, int nwaves) {
+                   int nc0, int nc1, int ntx, int nwaves, long long csc, long long csf) {
+  uc += blockIdx.y * csc;
+  uf += blockIdx.y * csf;
   const int lane = threadIdx.x;
   const int wpl = ntx * ((nc1 + 3) >> 2);
   const long long wg = xcd_band(blockIdx.x, wpl);
@@ -175,12 +182,13 @@ extern "C" int examg_debug_cell_narrow(int on) {
 }
 #endif
 
-extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
-                                   uint32_t face_mask, examg_stream_t stream) {
-  if (!l || !x || !g) { set_error("examg_apply_bc_cell: null argument"); return 1; }
-  if (kind != EXAMG_BC_DIRICHLET && kind != EXAMG_BC_NEUMANN && kind != EXAMG_BC_NEGATE) { set_error("examg_apply_bc_cell: unknown kind %d", kind); return 1; }
+// ncomp > 1: every component of a vector-valued field (examg_vec_*), the component the y dimension of the grid
+static int apply_bc_cell_impl(const char *who, const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
+                              uint32_t face_mask, examg_stream_t stream, int ncomp) {
+  if (!l || !x || !g) { set_error("%s: null argument", who); return 1; }
+  if (kind != EXAMG_BC_DIRICHLET && kind != EXAMG_BC_NEUMANN && kind != EXAMG_BC_NEGATE) { set_error("%s: unknown kind %d", who, kind); return 1; }
   if (kind == EXAMG_BC_DIRICHLET && !expr_ok(expr)) return 1;
-  if (!cell_layout_ok("examg_apply_bc_cell", l)) return 1;
+  if (!cell_layout_ok(who, l)) return 1;
   CellFaces fc;
   fc.n = 0;
   fc.start[0] = 0;
@@ -188,7 +196,7 @@ extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const exa
     for (int side = 0; side < 2; ++side) {
       if (!(face_mask & (1u << (2 * d + side)))) continue;
       if ((side ? l->ghost_r[d] : l->ghost_l[d]) < 1) {
-        set_error("examg_apply_bc_cell: face %d of dim %d has no ghost layer", side, d);
+        set_error("%s: face %d of dim %d has no ghost layer", who, side, d);
         return 1;
       }
       int b[3] = {0, 0, 0}, e[3] = {1, 1, 1};
@@ -219,79 +227,122 @@ extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const exa
   long long nb = (total + 255) / 256;
   if (nb > 2048) nb = 2048;
   hipStream_t s = (hipStream_t)stream;
+  const dim3 grid((unsigned)nb, ncomp);
+  const LayoutDev ld = make_layout(l);
+  const long long cs = ncomp > 1 ? ld.size : 0;
   if (kind == EXAMG_BC_NEUMANN)
-    hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_NEUMANN>), dim3((unsigned)nb), dim3(256), 0, s, make_layout(l), x, make_geom(g), fn, fc, inner);
+    hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_NEUMANN>), grid, dim3(256), 0, s, ld, x, make_geom(g), fn, fc, inner, cs);
   else if (kind == EXAMG_BC_NEGATE)
-    hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_NEGATE>), dim3((unsigned)nb), dim3(256), 0, s, make_layout(l), x, make_geom(g), fn, fc, inner);
+    hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_NEGATE>), grid, dim3(256), 0, s, ld, x, make_geom(g), fn, fc, inner, cs);
   else
-    hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_DIRICHLET>), dim3((unsigned)nb), dim3(256), 0, s, make_layout(l), x, make_geom(g), fn, fc, inner);
+    hipLaunchKernelGGL((k_apply_bc_cell<EXAMG_BC_DIRICHLET>), grid, dim3(256), 0, s, ld, x, make_geom(g), fn, fc, inner, cs);
   EXAMG_CHECK_LAUNCH("k_apply_bc_cell");
   return 0;
 }
 
-extern "C" int examg_restrict_cell(const examg_layout_t *lf_, const double *rf, const examg_layout_t *lc_, double *fc, double scale,
-                                   const int32_t *begin, const int32_t *end, examg_stream_t stream) {
-  if (!lf_ || !rf || !lc_ || !fc || !begin || !end) { set_error("examg_restrict_cell: null argument"); return 1; }
+extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
+                                   uint32_t face_mask, examg_stream_t stream) {
+  return apply_bc_cell_impl("examg_apply_bc_cell", l, x, g, kind, expr, face_mask, stream, 1);
+}
+
+extern "C" int examg_vec_apply_bc_cell(int n, const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, uint32_t face_mask,
+                                       examg_stream_t stream) {
+  if (!l) { set_error("examg_vec_apply_bc_cell: null argument"); return 1; }
+  if (!vec_fields_ok("examg_vec_apply_bc_cell", n, l, nullptr)) return 1;
+  if (kind != EXAMG_BC_NEUMANN) { set_error("examg_vec_apply_bc_cell: kind %d; vector-valued fields take EXAMG_BC_NEUMANN only", kind); return 1; }
+  return apply_bc_cell_impl("examg_vec_apply_bc_cell", l, x, g, kind, nullptr, face_mask, stream, n);
+}
+
+static int restrict_cell_impl(const char *who, const examg_layout_t *lf_, const double *rf, const examg_layout_t *lc_, double *fc, double scale, const int32_t *begin,
+                              const int32_t *end, examg_stream_t stream, int ncomp) {
+  if (!lf_ || !rf || !lc_ || !fc || !begin || !end) { set_error("%s: null argument", who); return 1; }
   // the dimensionality first: cell_layout_ok walks the nd dimensions of the per-dimension arrays, and nd = 4 would run as 2-D
-  if (lf_->nd != lc_->nd || (lf_->nd != 2 && lf_->nd != 3)) { set_error("examg_restrict_cell: 2-D or 3-D layouts of one dimensionality"); return 1; }
-  if (!cell_layout_ok("examg_restrict_cell", lf_) || !cell_layout_ok("examg_restrict_cell", lc_)) return 1;
+  if (lf_->nd != lc_->nd || (lf_->nd != 2 && lf_->nd != 3)) { set_error("%s: 2-D or 3-D layouts of one dimensionality", who); return 1; }
+  if (!cell_layout_ok(who, lf_) || !cell_layout_ok(who, lc_)) return 1;
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   const int nd = lf_->nd;
   const Box fine{2 * box.b0, 2 * box.b1, nd == 3 ? 2 * box.b2 : 0, 2 * box.e0, 2 * box.e1, nd == 3 ? 2 * box.e2 : 1};
-  if (!box_inside(lc_, box, 0) || !box_inside(lf_, fine, 0)) { set_error("examg_restrict_cell: box leaves an allocation"); return 1; }
-  if (nd == 2 && (box.b2 != 0 || box.e2 != 1)) { set_error("examg_restrict_cell: 2-D box must have [0,1) in dim 2"); return 1; }
+  if (!box_inside(lc_, box, 0) || !box_inside(lf_, fine, 0)) { set_error("%s: box leaves an allocation", who); return 1; }
+  if (nd == 2 && (box.b2 != 0 || box.e2 != 1)) { set_error("%s: 2-D box must have [0,1) in dim 2", who); return 1; }
   const double wgt = scale * (nd == 3 ? 0.125 : 0.25);
   const int ntx = (box.n0() + 63) / 64;
   const long long nwaves = (long long)box.n1() * box.n2();
   const long long nwg = (long long)ntx * ((box.n1() + 3) / 4) * box.n2();
-  if (nwg > 0x7fffffffLL) { set_error("examg_restrict_cell: grid too large"); return 1; }
-  const bool vec = !g_force_narrow && pairs_aligned(lf_, rf);
+  if (nwg > 0x7fffffffLL) { set_error("%s: grid too large", who); return 1; }
   const LayoutDev lf = make_layout(lf_), lc = make_layout(lc_);
+  // every component's pairs: an odd size(lfine) puts every other component on the 8-byte form, and then all of them
+  const bool vec = !g_force_narrow && pairs_aligned(lf_, rf) && (ncomp == 1 || (lf.size & 1) == 0);
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)nwg), blk(64, 4);
+  const dim3 grid((unsigned)nwg, ncomp), blk(64, 4);
+  const long long csf = ncomp > 1 ? lf.size : 0, csc = ncomp > 1 ? lc.size : 0;
   if (nd == 3) {
-    if (vec) hipLaunchKernelGGL((k_restrict_cell<3, true>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves);
-    else hipLaunchKernelGGL((k_restrict_cell<3, false>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves);
+    if (vec) hipLaunchKernelGGL((k_restrict_cell<3, true>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves, csf, csc);
+    else hipLaunchKernelGGL((k_restrict_cell<3, false>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves, csf, csc);
   } else {
-    if (vec) hipLaunchKernelGGL((k_restrict_cell<2, true>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves);
-    else hipLaunchKernelGGL((k_restrict_cell<2, false>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves);
+    if (vec) hipLaunchKernelGGL((k_restrict_cell<2, true>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves, csf, csc);
+    else hipLaunchKernelGGL((k_restrict_cell<2, false>), grid, blk, 0, s, lf, rf, lc, fc, wgt, box, ntx, (int)nwaves, csf, csc);
   }
   EXAMG_CHECK_LAUNCH("k_restrict_cell");
   return 0;
 }
 
-extern "C" int examg_prolong_add_cell(const examg_layout_t *lc_, const double *uc, const examg_layout_t *lf_, double *uf,
-                                      const int32_t *begin, const int32_t *end, examg_stream_t stream) {
-  if (!lc_ || !uc || !lf_ || !uf || !begin || !end) { set_error("examg_prolong_add_cell: null argument"); return 1; }
+extern "C" int examg_restrict_cell(const examg_layout_t *lf_, const double *rf, const examg_layout_t *lc_, double *fc, double scale,
+                                   const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  return restrict_cell_impl("examg_restrict_cell", lf_, rf, lc_, fc, scale, begin, end, stream, 1);
+}
+
+extern "C" int examg_vec_restrict_cell(int n, const examg_layout_t *lf_, const double *rf, const examg_layout_t *lc_, double *fc, double scale,
+                                       const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  if (!lf_ || !lc_) { set_error("examg_vec_restrict_cell: null argument"); return 1; }
+  if (!vec_fields_ok("examg_vec_restrict_cell", n, lf_, lc_)) return 1;
+  return restrict_cell_impl("examg_vec_restrict_cell", lf_, rf, lc_, fc, scale, begin, end, stream, n);
+}
+
+static int prolong_add_cell_impl(const char *who, const examg_layout_t *lc_, const double *uc, const examg_layout_t *lf_, double *uf, const int32_t *begin,
+                                 const int32_t *end, examg_stream_t stream, int ncomp) {
+  if (!lc_ || !uc || !lf_ || !uf || !begin || !end) { set_error("%s: null argument", who); return 1; }
   // the dimensionality first: cell_layout_ok walks the nd dimensions of the per-dimension arrays, and nd = 4 would run as 2-D
-  if (lf_->nd != lc_->nd || (lf_->nd != 2 && lf_->nd != 3)) { set_error("examg_prolong_add_cell: 2-D or 3-D layouts of one dimensionality"); return 1; }
-  if (!cell_layout_ok("examg_prolong_add_cell", lf_) || !cell_layout_ok("examg_prolong_add_cell", lc_)) return 1;
+  if (lf_->nd != lc_->nd || (lf_->nd != 2 && lf_->nd != 3)) { set_error("%s: 2-D or 3-D layouts of one dimensionality", who); return 1; }
+  if (!cell_layout_ok(who, lf_) || !cell_layout_ok(who, lc_)) return 1;
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   const int nd = lf_->nd;
-  if (nd == 2 && (box.b2 != 0 || box.e2 != 1)) { set_error("examg_prolong_add_cell: 2-D box must have [0,1) in dim 2"); return 1; }
+  if (nd == 2 && (box.b2 != 0 || box.e2 != 1)) { set_error("%s: 2-D box must have [0,1) in dim 2", who); return 1; }
   // parent box: floor(i / 2) over the fine box (arithmetic shifts floor negative indices too)
   const int cb0 = box.b0 >> 1, cb1 = box.b1 >> 1, cb2 = nd == 3 ? box.b2 >> 1 : 0;
   const int ce0 = ((box.e0 - 1) >> 1) + 1, ce1 = ((box.e1 - 1) >> 1) + 1, ce2 = nd == 3 ? ((box.e2 - 1) >> 1) + 1 : 1;
   const Box cbox{cb0, cb1, cb2, ce0, ce1, ce2};
-  if (!box_inside(lf_, box, 0) || !box_inside(lc_, cbox, 0)) { set_error("examg_prolong_add_cell: box leaves an allocation"); return 1; }
+  if (!box_inside(lf_, box, 0) || !box_inside(lc_, cbox, 0)) { set_error("%s: box leaves an allocation", who); return 1; }
   const int nc0 = ce0 - cb0, nc1 = ce1 - cb1, nc2 = ce2 - cb2;
   const int ntx = (nc0 + 63) / 64;
   const long long nwaves = (long long)nc1 * nc2;
   const long long nwg = (long long)ntx * ((nc1 + 3) / 4) * nc2;
-  if (nwg > 0x7fffffffLL) { set_error("examg_prolong_add_cell: grid too large"); return 1; }
-  const bool vec = !g_force_narrow && pairs_aligned(lf_, uf);
+  if (nwg > 0x7fffffffLL) { set_error("%s: grid too large", who); return 1; }
   const LayoutDev lc = make_layout(lc_), lf = make_layout(lf_);
+  const bool vec = !g_force_narrow && pairs_aligned(lf_, uf) && (ncomp == 1 || (lf.size & 1) == 0);   // every component's pairs
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid((unsigned)nwg), blk(64, 4);
+  const dim3 grid((unsigned)nwg, ncomp), blk(64, 4);
+  const long long csc = ncomp > 1 ? lc.size : 0, csf = ncomp > 1 ? lf.size : 0;
   if (nd == 3) {
-    if (vec) hipLaunchKernelGGL((k_prolong_add_cell<3, true>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves);
-    else hipLaunchKernelGGL((k_prolong_add_cell<3, false>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves);
+    if (vec) hipLaunchKernelGGL((k_prolong_add_cell<3, true>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves, csc, csf);
+    else hipLaunchKernelGGL((k_prolong_add_cell<3, false>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves, csc, csf);
   } else {
-    if (vec) hipLaunchKernelGGL((k_prolong_add_cell<2, true>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves);
-    else hipLaunchKernelGGL((k_prolong_add_cell<2, false>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves);
+    if (vec) hipLaunchKernelGGL((k_prolong_add_cell<2, true>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves, csc, csf);
+    else hipLaunchKernelGGL((k_prolong_add_cell<2, false>), grid, blk, 0, s, lc, uc, lf, uf, box, cb0, cb1, cb2, nc0, nc1, ntx, (int)nwaves, csc, csf);
   }
   EXAMG_CHECK_LAUNCH("k_prolong_add_cell");
   return 0;
+}
+
+extern "C" int examg_prolong_add_cell(const examg_layout_t *lc_, const double *uc, const examg_layout_t *lf_, double *uf,
+                                      const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  return prolong_add_cell_impl("examg_prolong_add_cell", lc_, uc, lf_, uf, begin, end, stream, 1);
+}
+
+extern "C" int examg_vec_prolong_add_cell(int n, const examg_layout_t *lc_, const double *uc, const examg_layout_t *lf_, double *uf,
+                                          const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  if (!lc_ || !lf_) { set_error("examg_vec_prolong_add_cell: null argument"); return 1; }
+  if (!vec_fields_ok("examg_vec_prolong_add_cell", n, lc_, lf_)) return 1;
+  return prolong_add_cell_impl("examg_vec_prolong_add_cell", lc_, uc, lf_, uf, begin, end, stream, n);
 }

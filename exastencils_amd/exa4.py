@@ -74,9 +74,10 @@ from .exa4_fusion import LazyFusions  # noqa: E402
 from .exa4_peepholes import Peepholes  # noqa: E402
 from .exa4_conservation import Conservation, _EXPR, expand  # noqa: E402
 from .exa4_complex import ComplexFields  # noqa: E402
+from .exa4_vector import VectorFields  # noqa: E402
 
 
-class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSystems, Nonlinear, Conservation, ComplexFields):
+class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSystems, Nonlinear, Conservation, ComplexFields, VectorFields):
     """One ExaSlang-4 program bound to a kernel layer (`ops`: HipOps on the GPU), a block decomposition and a
     communicator.  `run()` executes `Function Application`; printed lines are collected in `self.out`."""
 
@@ -164,6 +165,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
         self._complex_scratch: Dict[int, Field] = {}     # per level: the real field a `C = <real point expression>` loop fills first
         self._bc_depth = 0          # inside a boundary function that `apply bc` runs
         self._cell_names = set()    # fields declared on a cell layout: never taken by a one-pass peephole or cross-statement fusion
+        self._vector_names = set()  # fields declared on a vector-valued cell layout (exa4_vector.py)
+        self._has_vector = False    # ... or a stencil whose entries are matrices: only then is a statement asked whether it names one
         self._lazy_init()           # pending loops of the cross-statement fusions (exastencils_amd/exa4_fusion.py)
         self._declare()
 
@@ -201,6 +204,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
             self.functions.setdefault(fn.name, []).append(fn)
         self._inline_global_exprs()       # `Expr` macros of the Globals blocks (exa4_conservation.py)
         for name, e in a.globals:
+            if _contains(e, ("mat", "colvec")):
+                raise Exa4Unsupported("global %s: matrix-typed Var / Val (vector-valued fields run, matrix values do not)" % name)
             self.globals[name] = self._eval(e, _Frame(None, {}))
         layouts = {l.name: l for l in a.layouts}
         nslots: Dict[str, int] = {}
@@ -215,9 +220,13 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
             if ld.datatype == "Complex":
                 self._declare_complex_field(fd, ld, nslots[fd.name], sfield_fields)
                 continue
+            vector = (ld.vec_len != 1 or ld.vec_cols != 1) and fd.name not in sfield_fields
+            if vector and ld.localization != "Node":      # column vectors on cell fields run (exa4_vector.py); every other one is refused there
+                self._declare_vector_field(fd, ld, nslots[fd.name])
+                continue
             if ld.localization not in ("Node", "Cell"):
                 raise Exa4Unsupported("layout %s: localization %s (node and cell fields only)" % (ld.name, ld.localization))
-            if ld.vec_len != 1 and fd.name not in sfield_fields:
+            if vector:
                 raise Exa4Unsupported("vector-valued field %s outside a StencilField" % fd.name)
             if ld.localization == "Cell":
                 if self.grid is not None:
@@ -259,6 +268,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
                 self.transfer[sd.name] = sd.transfer
                 self.transfer_factor[sd.name] = float(sd.transfer_factor)
         self._stencil_decls = {s.name: s for s in a.stencils if not s.transfer}
+        self._has_vector = bool(self._vector_names) or any(self._is_matrix_stencil(n) for n in self._stencil_decls)
         # a name declared once per level (`Stencil A@3 {..}  Stencil A@4 {..}`: the layer-4 text generated from layer 3)
         self._stencil_decl_at = {}
         for sd in a.stencils:
@@ -686,7 +696,11 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
         if name in _MATH and name not in self.functions:
             return _MATH[name](*[self._eval(a, fr) for a in args])
         if name.split("_")[0] in ("printField", "writeField", "readField") and name not in self.functions:
+            if self._has_vector and any(self._touches_vector(x) for x in args):
+                raise Exa4Unsupported("%s: field I/O of vector-valued fields" % name)
             return self._field_io(name, args, fr)
+        if self._has_vector and name not in self.functions and any(self._touches_vector(x) for x in args):
+            raise Exa4Unsupported("%s ( .. ) outside a recognised loop: values of vector-valued fields and matrix stencils live in loop bodies" % name)
         if name in ("startTimer", "stopTimer", "getTotalFromTimer", "getTotalTime", "getMeanFromTimer") and args and \
                 args[0][0] == "id" and args[0][1] not in fr.vars and args[0][1] not in self.globals:
             # timers may be named by a bare identifier (Testing/PolyExpl/Jac3Dcc.exa4:49: startTimer(benchTimer))
@@ -1045,6 +1059,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
         if self._pending is not None and self._gate(s, fr):
             return
         if k == "decl":
+            if s[2] is not None and self._has_vector and self._touches_vector(s[2]):
+                raise Exa4Unsupported("variable %s: matrix-typed Var / Val and values of vector-valued fields outside a loop" % s[1])
             fr.vars[s[1]] = self._eval(s[2], fr) if s[2] is not None else 0
         elif k == "exprdecl":
             fr.vars[_EXPR + s[1]] = s[3]      # a macro: substituted where it is used (exa4_conservation.py)
@@ -1063,7 +1079,7 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
             if s[1] == "finish":
                 return
             f, slot = self._field(s[3], fr)
-            if f.layout.is_complex:      # one block without periodic axes (checked where the field is declared): nothing to exchange
+            if f.layout.is_complex or f.layout.is_vector:      # one block without periodic axes (checked where the field is declared): nothing to exchange
                 return
             self.comm.exchange(f, slot, s[2])
         elif k == "applybc":
@@ -1083,6 +1099,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
             if s[2]:
                 fr.vars[s[2]] = n
         elif k == "contract":
+            if self._has_vector and self._touches_vector(("block", list(s[5]))):
+                raise Exa4Unsupported("repeat ... with contraction over vector-valued fields")
             self._exec_contract(s, fr)
         elif k == "until":
             while not self._eval(s[1], fr):
@@ -1185,6 +1203,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
                                   % (st[2][1], st[1], what))
 
     def _apply_bc(self, f: Field, slot: int):
+        if f.layout.is_vector:
+            return self._apply_bc_vector(f, slot)
         if f.layout.is_cell:
             # a ghost value is a function of the interior: written every time, never assumed valid
             mask = self.domain.face_mask()
@@ -1289,6 +1309,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
     def _exec_loop(self, s, fr: _Frame):
         _, target, only, where, reduction, body = s
         f, _ = self._field(target, fr)
+        if self._has_vector and (f.layout.is_vector or self._touches_vector(("block", list(body)))):
+            return self._exec_vector_loop(s, f, fr)      # (exa4_vector.py)
         ghost = self._recognise_ghost_loop(s, f, fr)      # a boundary function's loop over one face (exa4_conservation.py)
         if ghost is not None:
             return self._launch(ghost, None, None, None)

@@ -75,6 +75,8 @@ class LayoutDecl:
     ghost_comm: bool = False
     dup_comm: bool = False
     inner: Tuple[int, ...] = ()
+    vec_cols: int = 1          # `Matrix< Real, rows, cols >`: vec_len is the rows; every other spelling of a vector has one column
+    vec_elem: str = "Real"     # the element type of `Vector< T, n >` / `Matrix< T, r, c >` as written (`Complex< Real >` is "Complex")
 
 
 @dataclass
@@ -94,6 +96,7 @@ class StencilDecl:
     entries: List[Tuple[Tuple[int, ...], object]] = _dcf(default_factory=list)   # (offset, coefficient expression)
     transfer: Optional[str] = None      # 'restriction' | 'prolongation'
     transfer_factor: float = 1.0        # the common factor on the weights of a node restriction (examg_restrict's scale)
+    from_expr: object = None            # `Stencil S from ( 2.0 * A + B )`: stencil arithmetic, evaluated on the host (exa4_vector.py)
 
 
 @dataclass
@@ -276,22 +279,29 @@ class Parser:
         self.expect("Layout")
         name = self.ident()
         self.expect("<")
-        dt, vec = self.ident(), 1
+        dt, vec, cols, elem = self.ident(), 1, 1, "Real"
         if dt == "Complex" and self.accept("<"):      # Complex<Real> | Complex<Double>: (re, im) per point
             inner = self.ident()
             if inner not in ("Real", "Double"):
                 raise Exa4Unsupported("layout %s: Complex<%s> (double precision only)" % (name, inner))
             self.expect(">")
-        elif self.accept("<"):        # ColumnVector<Real,7>
-            self.ident()
+        elif self.accept("<"):        # ColumnVector<Real,7> | Vector<Real,3> | Matrix<Real,2,1>
+            elem = self.ident()
+            if elem == "Complex" and self.accept("<"):      # Vector< Complex< Real >, 2 >
+                self.ident()
+                self.expect(">")
             self.expect(",")
             vec = int(self.next().text)
+            if self.accept(","):
+                cols = int(self.next().text)
             self.expect(">")
+        elif dt in ("Vec2", "Vec3", "Vec4"):      # the short names of column vectors: never a scalar layout
+            vec = int(dt[3])
         self.expect(",")
         loc = self.ident()
         self.expect(">")
         levels = self.decl_levels()
-        d = LayoutDecl(name, dt, vec, loc, levels)
+        d = LayoutDecl(name, dt, vec, loc, levels, vec_cols=cols, vec_elem=elem)
         self.expect("{")
         while not self.accept("}"):
             key = self.ident()
@@ -335,6 +345,10 @@ class Parser:
         self.expect("Stencil")
         name = self.ident()
         levels = self.decl_levels() if self.at("@") else None      # `Stencil R@all from default ..` (Testing/NonLinear/FAS_2D_Basic.exa4:30)
+        if self.at("from") and self.at("(", 1):      # `Stencil S@all from ( ( alpha ** 2 ) * Laplace + gradContribution )`
+            self.next()
+            self.stencils.append(StencilDecl(name, levels, from_expr=self.expr()))
+            return
         if self.accept("from"):
             self.expect("default")
             kind = self.ident()
@@ -748,6 +762,26 @@ class Parser:
             e = self.expr()
             self.expect(")")
             return e
+        if t.text == "{":
+            # `{ { a, b }, { c, d } }`: a matrix, rows of elements; `{ e0, e1 }T`: the transposed row, a column vector
+            items, nested = [], self.at("{")
+            while not self.accept("}"):
+                if nested:
+                    self.expect("{")
+                    row = []
+                    while not self.accept("}"):
+                        row.append(self.expr())
+                        self.accept(",")
+                    items.append(row)
+                else:
+                    items.append(self.expr())
+                self.accept(",")
+            if nested:
+                return ("mat", items)
+            if self.at("T") and self.peek().kind == "id":
+                self.next()
+                return ("colvec", items)
+            return ("mat", [items])      # a row vector: a matrix of one row
         if t.kind != "id":
             raise Exa4SyntaxError("line %d: unexpected %r in an expression" % (t.line, t.text))
         name = t.text
@@ -791,6 +825,11 @@ class Parser:
         if off is not None:
             return ("off", ("fld", name, slot, level) if name in self.field_names else ("id", name, level), off)
         if name in self.field_names:
+            if self.at("[") and self.peek(1).kind == "num" and self.at("]", 2):      # `flow[0]`: one component of a vector-valued field
+                self.next()
+                c = int(self.next().text)
+                self.next()
+                return ("comp", ("fld", name, slot, level), c)
             return ("fld", name, slot, level)
         if name in self.stencil_names or name in self.sfield_names:
             if self.at(":") and self.at("[", 1):

@@ -21,7 +21,8 @@ from .field import Field, Stencil
 class LoopStmt:
     """What one assignment in a loop body launches.  kind: set | fill_fn | fill_expr | fill_expr_cell | copy | axpby | add_scalar |
     residual | apply | smooth | restrict | restrict_cell | prolong_add | prolong_add_cell | sys_row | pointwise_mul | pointwise_sub |
-    bsys_row | nl_op | nl_smooth | axis_residual | axis_apply | axis_smooth | flux_step | reduce_expr | bc_face."""
+    bsys_row | nl_op | nl_smooth | axis_residual | axis_apply | axis_smooth | flux_step | reduce_expr | bc_face | v_set | v_axpby | v_op |
+    v_smooth | v_restrict_cell | v_prolong_add_cell | v_components."""
     kind: str
     D: Field                        # the field assigned to
     ds: int
@@ -126,6 +127,8 @@ class Statements:
         evaluated here; nothing is launched or counted.  `colour`: the red-black colour of the loop, for the forms whose refusals
         depend on it (system rows, semilinear operators); what a smoother needs of it is checked where it is launched."""
         op, lhs, rhs = st[1], st[2], st[3]
+        if self._has_vector and self._touches_vector(st):      # vector-valued cell fields: the kinds v_* (exa4_vector.py)
+            return self._recognise_vector(st, fr, colour)
         if lhs[0] != "fld":
             raise Exa4Unsupported("loop body assigns to %s" % lhs[0])
         D, ds = self._field(lhs, fr)
@@ -255,6 +258,8 @@ class Statements:
         D, U, F = k.D, k.U, k.F
         if kind.startswith("c_"):             # (exa4_complex.py) a loop over complex fields
             return self._launch_complex(k, b, e, colour)
+        if kind.startswith("v_"):             # (exa4_vector.py) a loop over vector-valued cell fields: one launch over all components
+            return self._launch_vector(k, b, e, colour)
         if kind == "bc_face":                 # (exa4_conservation.py) one face of a boundary function; no face: the block has a neighbour there
             if k.prog[1]:
                 self.launches += 1

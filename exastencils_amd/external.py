@@ -20,6 +20,10 @@ class ExternalField:
             from .exa4_parser import Exa4Unsupported
 
             raise Exa4Unsupported("external field %s on %s: external fields of complex type (the copy kernels move real fields)" % (name, target.name))
+        if layout.is_vector or target.layout.is_vector:
+            from .exa4_parser import Exa4Unsupported
+
+            raise Exa4Unsupported("external field %s on %s: external fields of vector-valued type (the copy kernels move one scalar plane)" % (name, target.name))
         self.name, self.layout, self.target, self.ops = name, layout, target, ops
         self.lc = layout.c_struct()
         self._stage = None

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field as _dc_field
 from typing import List, Optional, Sequence, Tuple
 
 from .layout import FieldLayout
-from .lib import ColouringC, StencilC
+from .lib import VEC_MAX, ColouringC, StencilC, VecStencilC
 
 # Named point functions of the reference's programs (boundary values, right-hand sides, exact solutions, coefficient profiles).
 # They are HOST-side names only: the library knows expression programs (examg_expr_t) and nothing else -- FN_PROGRAMS below
@@ -32,8 +32,21 @@ class Field:
         self.name, self.level, self.layout, self.num_slots = name, level, layout, num_slots
         self.bc_fn, self.bc_params = bc_fn, tuple(bc_params)
         self.lc = layout.c_struct()
+        # a vector-valued layout (FieldLayout.as_vector): layout.doubles = ncomp * size, every component zeroed
         self.slots = [ops.new_array(layout.doubles) for _ in range(num_slots)]   # initFieldsWithZero; a complex layout: (re, im) per point
         self.current_slot = 0
+
+    @classmethod
+    def view_of(cls, name: str, level: int, layout: FieldLayout, array) -> "Field":
+        """A one-slot field over an array that exists (a component plane of a vector-valued field): nothing is allocated."""
+        class _Given:
+            @staticmethod
+            def new_array(n):
+                if int(n) != int(array.numel() if hasattr(array, "numel") else len(array)):
+                    raise ValueError("a view of %d values for a layout of %d" % (len(array), n))
+                return array
+
+        return cls(name, level, layout, _Given, 1, None, ())
 
     @property
     def active(self) -> int:
@@ -45,6 +58,15 @@ class Field:
 
     def advance(self):
         self.current_slot = (self.current_slot + 1) % self.num_slots
+
+    def component(self, c: int, slot: Optional[int] = None):
+        """(layout, array) of component c of a vector-valued field: the scalar layout and a view of the plane at c * size -- what every
+        scalar entry point takes."""
+        n = self.layout.ncomp
+        if not 0 <= c < n:
+            raise IndexError("component %d of a field of %d" % (c, n))
+        size = self.layout.size
+        return self.layout.scalar(), self.data(slot)[c * size:(c + 1) * size]
 
     def data(self, slot: Optional[int] = None):
         return self.slots[self.current_slot if slot is None else slot]
@@ -125,6 +147,48 @@ class Stencil:
                 s.wform = int(self.wform)
         else:
             s.cfield = None
+        return s
+
+
+@dataclass
+class MatrixStencil:
+    """A stencil whose entries are n x n matrices (`[0, 0] => { { IxIx, IxIy }, { IxIy, IyIy } }`), on a vector-valued cell field.
+    elems[k][c][d] is None (the element is absent) or (constant or None, device array of a cell coefficient field or None): both
+    stand for constant + field, evaluated per cell.  glayout: the layout of every coefficient field."""
+    n: int
+    offsets: List[Tuple[int, int, int]]
+    elems: List[List[List[Optional[tuple]]]]
+    glayout: Optional[FieldLayout] = None
+
+    @property
+    def centre_index(self) -> int:
+        return self.offsets.index((0, 0, 0))
+
+    def c_struct(self, ptr_of, lu=None) -> VecStencilC:
+        """lu: the layout the coefficient layout defaults to when the stencil has no coefficient field."""
+        s = VecStencilC()
+        s.nent = len(self.offsets)
+        gl = self.glayout if self.glayout is not None else lu
+        if gl is not None:
+            s.lg = gl.c_struct() if isinstance(gl, FieldLayout) else gl
+        n = self.n
+        for k, o in enumerate(self.offsets[:7]):
+            en = s.ent[k]
+            for d in range(3):
+                en.off[d] = o[d]
+            mask = 0
+            for c in range(min(n, VEC_MAX)):
+                for d in range(min(n, VEC_MAX)):
+                    el = self.elems[k][c][d]
+                    if el is None:
+                        continue
+                    kv, g = el
+                    if kv is not None:
+                        mask |= 1 << (c * n + d)
+                        en.k[c * n + d] = float(kv)
+                    if g is not None:
+                        en.g[c * n + d] = ptr_of(g)
+            en.kmask = mask
         return s
 
 

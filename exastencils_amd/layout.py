@@ -34,6 +34,30 @@ class FieldLayout:
     # "real" | "complex": Python-side only, like the localization.  A point of a complex field is two consecutive doubles (re, im); every
     # count of the layout stays in POINTS and the element kind travels as the choice of entry point (examg_c*: include/examg.h).
     element: str = "real"
+    # components of a vector-valued field (`Layout X< Vec2, Cell >`): Python-side only.  The C struct is the scalar one; component c of a
+    # field lives at c * size doubles (the component is the slowest array dimension, field/l4/L4_FieldLayout.scala:63-73) and the count
+    # travels as the argument n of the examg_vec_* entry points.
+    ncomp: int = 1
+
+    @property
+    def is_vector(self) -> bool:
+        return self.ncomp > 1
+
+    def as_vector(self, n: int) -> "FieldLayout":
+        """This layout for a column vector of n components per cell."""
+        from dataclasses import replace
+
+        if n not in (2, 3):
+            raise ValueError("vector-valued fields have 2 or 3 components, not %r" % (n,))
+        if not self.is_cell or self.transform or self.is_complex:
+            raise ValueError("vector-valued fields are real cell fields in the untransformed layout")
+        return replace(self, ncomp=int(n))
+
+    def scalar(self) -> "FieldLayout":
+        """The layout of one component."""
+        from dataclasses import replace
+
+        return replace(self, ncomp=1) if self.ncomp > 1 else self
 
     @property
     def is_cell(self) -> bool:
@@ -46,7 +70,7 @@ class FieldLayout:
     @property
     def doubles(self) -> int:
         """Doubles of an array of this layout: size points, two doubles each for a complex field."""
-        return (2 if self.is_complex else 1) * self.size
+        return (2 if self.is_complex else 1) * self.ncomp * self.size
 
     def as_complex(self) -> "FieldLayout":
         from dataclasses import replace

@@ -72,6 +72,20 @@ class SysC(C.Structure):
                 ("f", C.c_void_p * SYS_MAX), ("g", C.c_void_p * (SYS_MAX * SYS_MAX)), ("dst", C.c_void_p * SYS_MAX)]
 
 
+VEC_MAX = 3
+
+
+class VecEntryC(C.Structure):
+    """examg_vec_entry_t: one entry of a matrix stencil -- element (c, d) at index c * n + d: a constant (kmask bit), a cell coefficient
+    field (g), both or neither."""
+    _fields_ = [("off", C.c_int32 * 3), ("kmask", C.c_uint32), ("k", C.c_double * (VEC_MAX * VEC_MAX)), ("g", C.c_void_p * (VEC_MAX * VEC_MAX))]
+
+
+class VecStencilC(C.Structure):
+    """examg_vec_stencil_t: a matrix stencil on a vector-valued cell field (include/examg.h)."""
+    _fields_ = [("nent", C.c_int32), ("lg", LayoutC), ("ent", VecEntryC * 7)]
+
+
 BSYS_MAX = 3
 BSYS_GATHER = 1                           # what examg_bsys_route answers (-1 refused, 0 empty box)
 
@@ -193,6 +207,8 @@ SYMBOLS = [
     "examg_prolong_add_cell",
     "examg_stencil_op_coloured", "examg_mcgs_sweep", "examg_mcgs_one_pass_eligible",
     "examg_sys_op", "examg_sys_relax", "examg_pointwise_mul",
+    "examg_vec_op", "examg_vec_smooth", "examg_vec_dot", "examg_vec_set", "examg_vec_axpby", "examg_vec_restrict_cell",
+    "examg_vec_prolong_add_cell", "examg_vec_apply_bc_cell",
     "examg_bsys_op", "examg_bsys_relax", "examg_bsys_route",
     "examg_nl_op", "examg_nl_smooth",
     "examg_gs_sweep", "examg_gs_route",
@@ -328,6 +344,15 @@ def load(path=None):
     L.examg_sys_op.argtypes = [C.c_int, yp, sp, C.c_uint32, ip, ip, vp]
     L.examg_sys_relax.argtypes = [yp, sp, C.c_double, C.c_int, ip, ip, vp]
     L.examg_pointwise_mul.argtypes = [lp, vp, lp, vp, lp, vp, C.c_double, ip, ip, vp]
+    mp = C.POINTER(VecStencilC)
+    L.examg_vec_op.argtypes = [C.c_int, C.c_int, lp, vp, lp, vp, lp, vp, mp, ip, ip, vp]
+    L.examg_vec_smooth.argtypes = [C.c_int, lp, vp, lp, vp, mp, C.c_double, C.c_int, ip, ip, vp]
+    L.examg_vec_dot.argtypes = [C.c_int, lp, vp, lp, vp, ip, ip, vp, vp, vp]
+    L.examg_vec_set.argtypes = [C.c_int, lp, vp, C.c_double, ip, ip, vp]
+    L.examg_vec_axpby.argtypes = [C.c_int, lp, vp, lp, vp, C.c_double, C.c_double, ip, ip, vp]
+    L.examg_vec_restrict_cell.argtypes = [C.c_int, lp, vp, lp, vp, C.c_double, ip, ip, vp]
+    L.examg_vec_prolong_add_cell.argtypes = [C.c_int, lp, vp, lp, vp, ip, ip, vp]
+    L.examg_vec_apply_bc_cell.argtypes = [C.c_int, lp, vp, gp, C.c_int, C.c_uint32, vp]
     bp = C.POINTER(BsysC)
     L.examg_bsys_op.argtypes = [C.c_int, bp, C.c_uint32, ip, ip, vp]
     L.examg_bsys_relax.argtypes = [bp, C.c_double, cp, ip, ip, vp]
@@ -382,6 +407,9 @@ def load(path=None):
     if hasattr(L, "examg_debug_sys_narrow"):         # debug build only: the 8-byte form of the system kernels
         L.examg_debug_sys_narrow.argtypes = [C.c_int]
         L.examg_debug_sys_narrow.restype = C.c_int
+    if hasattr(L, "examg_debug_vec_narrow"):         # debug build only: the 8-byte form of the vector-field kernels
+        L.examg_debug_vec_narrow.argtypes = [C.c_int]
+        L.examg_debug_vec_narrow.restype = C.c_int
     if hasattr(L, "examg_debug_cg_route"):           # debug build only: the form of the one-kernel coarse solver, and which one a call takes
         L.examg_debug_cg.argtypes = [C.c_int]
         L.examg_debug_cg.restype = C.c_int

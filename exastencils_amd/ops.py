@@ -11,7 +11,7 @@ import ctypes as C
 from typing import Optional, Sequence
 
 from . import lib as _lib
-from .field import Colouring, Stencil, fn_expr  # noqa: F401  (Colouring: the value type of the coloured entry points)
+from .field import Colouring, MatrixStencil, Stencil, fn_expr  # noqa: F401  (Colouring: the value type of the coloured entry points)
 from .lib import NL_ADD, NL_APPLY, NL_RESIDUAL, ExamgError, check, ivec  # noqa: F401  (NL_*: the modes of nl_op)
 
 
@@ -357,6 +357,47 @@ class HipOps:
         """dst = (s * x) * y, s = +-1.0 (examg_pointwise_mul)."""
         check(self.L.examg_pointwise_mul(C.byref(lx), self.ptr(x), C.byref(ly), self.ptr(y), C.byref(ld), self.ptr(dst), float(s), ivec(begin),
                                          ivec(end), self._stream()), "examg_pointwise_mul")
+
+    # -- vector-valued cell fields: a vector argument is (layout, array of n * size doubles), the component slowest ---------------
+    def vec_op(self, mode: int, n: int, lu, u, lf, f, ld, dst, M: MatrixStencil, begin, end):
+        """dst = M * u (lib.SYS_APPLY) or f - M * u (lib.SYS_RESIDUAL), every row of the matrix stencil M in one launch (examg_vec_op)."""
+        mc = M.c_struct(self.ptr, lu)
+        check(self.L.examg_vec_op(int(mode), int(n), C.byref(lu), self.ptr(u), C.byref(lf) if lf is not None else None,
+                                  self.ptr(f) if f is not None else None, C.byref(ld), self.ptr(dst), C.byref(mc), ivec(begin), ivec(end),
+                                  self._stream()), "examg_vec_op")
+
+    def vec_smooth(self, n: int, lu, u, lf, f, M: MatrixStencil, relax: float, colour: int, begin, end):
+        """One colour of u = u + relax * (inverse(diag(M)) * (f - M * u)), in place (examg_vec_smooth)."""
+        mc = M.c_struct(self.ptr, lu)
+        check(self.L.examg_vec_smooth(int(n), C.byref(lu), self.ptr(u), C.byref(lf), self.ptr(f), C.byref(mc), float(relax), int(colour),
+                                      ivec(begin), ivec(end), self._stream()), "examg_vec_smooth")
+
+    def vec_dot(self, n: int, lx, x, ly, y, begin, end, out=None):
+        """sum over the box of dot(x, y) of the cell, on the device (examg_vec_dot)."""
+        out = self.new_scalar() if out is None else out
+        check(self.L.examg_vec_dot(int(n), C.byref(lx), self.ptr(x), C.byref(ly), self.ptr(y), ivec(begin), ivec(end), self.ptr(out),
+                                   self.ptr(self._work), self._stream()), "examg_vec_dot")
+        return out
+
+    def vec_set(self, n: int, l, x, v: float, begin, end):
+        check(self.L.examg_vec_set(int(n), C.byref(l), self.ptr(x), float(v), ivec(begin), ivec(end), self._stream()), "examg_vec_set")
+
+    def vec_axpby(self, n: int, lx, x, ly, y, a: float, b: float, begin, end):
+        check(self.L.examg_vec_axpby(int(n), C.byref(lx), self.ptr(x), C.byref(ly), self.ptr(y), float(a), float(b), ivec(begin), ivec(end),
+                                     self._stream()), "examg_vec_axpby")
+
+    def vec_restrict_cell(self, n: int, lfine, rf, lc, fc, scale: float, begin, end):
+        check(self.L.examg_vec_restrict_cell(int(n), C.byref(lfine), self.ptr(rf), C.byref(lc), self.ptr(fc), float(scale), ivec(begin),
+                                             ivec(end), self._stream()), "examg_vec_restrict_cell")
+
+    def vec_prolong_add_cell(self, n: int, lc, uc, lfine, uf, begin, end):
+        check(self.L.examg_vec_prolong_add_cell(int(n), C.byref(lc), self.ptr(uc), C.byref(lfine), self.ptr(uf), ivec(begin), ivec(end),
+                                                self._stream()), "examg_vec_prolong_add_cell")
+
+    def vec_apply_bc_cell(self, n: int, l, x, geom, kind: int, face_mask: int):
+        """ghost = interior on every face of the mask and every component, one launch (examg_vec_apply_bc_cell; lib.BC_NEUMANN only)."""
+        check(self.L.examg_vec_apply_bc_cell(int(n), C.byref(l), self.ptr(x), C.byref(geom), int(kind), int(face_mask), self._stream()),
+              "examg_vec_apply_bc_cell")
 
     # -- coupled systems of node fields whose blocks are stencils --------------------------------------
     def _bsys(self, lu, u, lf, f, A, ld=None, dst=None):

@@ -808,6 +808,86 @@ int examg_sys_relax(const examg_sys_t *sys, const examg_stencil_t *L, double rel
 int examg_pointwise_mul(const examg_layout_t *lx, const double *x, const examg_layout_t *ly, const double *y, const examg_layout_t *ld,
                         double *dst, double s, const int32_t *begin, const int32_t *end, examg_stream_t stream);
 
+/* ---- Vector-valued cell fields and matrix stencils ---------------------------------------------------------------------------
+ * `Layout X< Vec2, Cell >`, `Field flow< global, X, Neumann >`, `Stencil S { [0, 0] => { { IxIx, IxIy }, { IxIy, IyIy } }, .. }`
+ * (Testing/Application/OpticalFlow2D.exa4).  A vector field of n = 2 or 3 components in layout l is n scalar arrays one behind the other,
+ * the component slowest (field/l4/L4_FieldLayout.scala:63-73): component c lives at  base + c * size(l),  size(l) the doubles of
+ * one array of the layout (examg_layout_size).  A vector argument is (layout, base pointer); n is a call argument.  The layout
+ * struct is the scalar one.
+ *
+ * examg_vec_stencil_t, a MATRIX STENCIL M: 1 .. 7 entries, the centre (required) and axis neighbours at distance 1, each at most once, in
+ * any order; the order is significant.  Entry k is an n x n matrix, element (c, d) at index c * n + d:
+ *   kmask bit c*n+d   the element has the constant k[c*n+d]
+ *   g[c*n+d]          the element has a cell coefficient field (a scalar array in layout lg, read at the cell); NULL: none
+ *                     (lg is looked at only when some element has a field: a stencil of constants may leave it zeroed)
+ *   both: the element is  k_cd + g_cd(i),  evaluated at every cell; neither: the element is ABSENT
+ * An off-centre entry is a diagonal matrix of constants (its diagonal elements may differ per component, and may be absent); a
+ * coefficient field or an element off the diagonal there is an error.  Coefficient pointers that alias are loaded once.
+ *
+ * Arithmetic, fp64, no contraction.  With m_cd the element of entry k and o_k its offset:
+ *   t_k,c = the present elements of row c of entry k folded left to right in d over  m_cd * u_d(i + o_k)
+ *   Mu_c  = the t_k,c folded left to right in entry order
+ * Absent elements, and entries without a present element in row c, are skipped, not multiplied by zero; a row without any element
+ * gives Mu_c = 0.0.
+ *
+ * examg_vec_op, every row c and every cell of [begin,end) in one launch:
+ *   EXAMG_SYS_APPLY:    dst_c = Mu_c                  (`dst = S * u`)
+ *   EXAMG_SYS_RESIDUAL: dst_c = f_c - Mu_c            (`dst = f - S * u`)
+ * u, f and dst are vector fields in lu, lf and ld.  Reads u on the box and its one-cell axis shell, f and the coefficients on the box;
+ * writes the box of dst and nothing else.  dst may overlap neither u nor, in EXAMG_SYS_RESIDUAL, f.
+ *
+ * examg_vec_smooth: one colour (i0 + i1 + i2) % 2 == colour of
+ *     `u = u + relax * ( inverse ( diag ( S ) ) * ( f - S * u ) )`
+ * in place, inside `repeat with { colour conditions .. }` / `color with`:
+ *   r    = f - Mu exactly as EXAMG_SYS_RESIDUAL computes it (the centre entry included)
+ *   D    = the centre matrix, absent elements read as 0.0
+ *   x    solves D x = r with the n = 2 and n = 3 formulas of examg_sys_relax above
+ *   u_c  = u_c + x_c when relax == 1.0, else u_c + relax * x_c
+ * Reads only cells of the other colour and the cell's own values; writes the colour's cells of the box and nothing else.  As for
+ * examg_sys_relax, these are not the generator's bits (it emits an inverse times a vector; its results files carry four digits).
+ *
+ * examg_vec_dot: *result = sum over the box of the per-cell term ((x_0 * y_0) + (x_1 * y_1)) [+ (x_2 * y_2)] -- `v += dot ( x, y )`
+ * with `reduction ( + : v )` -- through the kernels, the fixed tree and the work buffer of examg_dot (the same launch plan as
+ * examg_dot on that box).
+ *
+ * examg_vec_set, examg_vec_axpby, examg_vec_restrict_cell, examg_vec_prolong_add_cell, examg_vec_apply_bc_cell: the scalar entry
+ * point's kernel over all n components in ONE launch; on every component the bits the scalar entry point writes when called on that
+ * component (same arguments otherwise, same checks).  examg_vec_apply_bc_cell knows EXAMG_BC_NEUMANN only.
+ *
+ * Refused before anything is launched: n outside 2 .. 3; a layout with duplicate layers or under a layout transformation; layouts of
+ * different inner sizes or dimensionality; unknowns without a ghost layer; an entry off the axes, of reach 2 or repeated; a stencil
+ * without a centre entry; an off-centre entry with an element off the diagonal or with a coefficient field; a box that leaves an
+ * allocation; a dst that overlaps an input; a BC kind other than Neumann.  An empty box is a no-op that returns 0 (examg_vec_dot:
+ * *result = 0).  Rows whose pairs of cells are 16-byte aligned in every argument and component are accessed 16 bytes at a time,
+ * others 8: the same bits either way. */
+#define EXAMG_VEC_MAX 3
+typedef struct examg_vec_entry {
+  int32_t off[3];
+  uint32_t kmask;
+  double k[EXAMG_VEC_MAX * EXAMG_VEC_MAX];
+  const double *g[EXAMG_VEC_MAX * EXAMG_VEC_MAX];
+} examg_vec_entry_t;
+typedef struct examg_vec_stencil {
+  int32_t nent;
+  examg_layout_t lg;
+  examg_vec_entry_t ent[7];
+} examg_vec_stencil_t;
+int examg_vec_op(int mode, int n, const examg_layout_t *lu, const double *u, const examg_layout_t *lf, const double *f, const examg_layout_t *ld,
+                 double *dst, const examg_vec_stencil_t *M, const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_vec_smooth(int n, const examg_layout_t *lu, double *u, const examg_layout_t *lf, const double *f, const examg_vec_stencil_t *M, double relax,
+                     int colour, const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_vec_dot(int n, const examg_layout_t *lx, const double *x, const examg_layout_t *ly, const double *y, const int32_t *begin,
+                  const int32_t *end, double *result, void *work, examg_stream_t stream);
+int examg_vec_set(int n, const examg_layout_t *l, double *x, double v, const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_vec_axpby(int n, const examg_layout_t *lx, const double *x, const examg_layout_t *ly, double *y, double a, double b,
+                    const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_vec_restrict_cell(int n, const examg_layout_t *lfine, const double *rf, const examg_layout_t *lcoarse, double *fc, double scale,
+                            const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_vec_prolong_add_cell(int n, const examg_layout_t *lcoarse, const double *uc, const examg_layout_t *lfine, double *uf,
+                               const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_vec_apply_bc_cell(int n, const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, uint32_t face_mask,
+                            examg_stream_t stream);
+
 /* ---- Coupled systems of node-centred unknowns whose blocks are stencils ------------------------------------------------------
  * n = 2 or 3 scalar node fields u_0 .. u_{n-1} and an n x n table of constant stencils: row c of the operator is
  *     Au_c = sum over d of A_cd * u_d

@@ -125,6 +125,27 @@ static inline bool vec_fields_ok(const char *who, int n, const examg_layout_t *l
   return true;
 }
 
+// Staggered grids (include/examg.h): what every entry point asks of the layout `what` of a staggered field -- a plain layout whose
+// duplicate layers are those of its localization: loc = -1 a cell layout (none), else a face layout of axis loc (one per side on the own
+// axis, none on the others).  The dimensions of l->nd are looked at (the caller has checked nd).  false: error text set.
+static inline bool staggered_layout_ok(const char *who, const char *what, const examg_layout_t *l, int loc) {
+  if (lay_split(l)) { set_error("%s: the %s layout is under a layout transformation; staggered fields take plain layouts only", who, what); return false; }
+  for (int d = 0; d < l->nd && d < 3; ++d) {
+    const int dup = d == loc ? 1 : 0;
+    if (l->dup_l[d] == dup && l->dup_r[d] == dup) continue;
+    if (loc < 0) set_error("%s: the %s layout is not a cell layout (dim %d has %d / %d duplicate layers)", who, what, d, l->dup_l[d], l->dup_r[d]);
+    else set_error("%s: the %s layout is not a face layout of axis %d (dim %d has %d / %d duplicate layers, a face layout has %d)", who, what, loc, d, l->dup_l[d], l->dup_r[d], dup);
+    return false;
+  }
+  return true;
+}
+// ... of the one layout of an entry point that takes the axis of a face field (kernels_mac.hip, kernels_blas.hip)
+static inline bool face_layout_ok(const char *who, const char *what, int axis, const examg_layout_t *l) {
+  if (l->nd != 2 && l->nd != 3) { set_error("%s: 2-D or 3-D layouts", who); return false; }
+  if (axis < 0 || axis >= l->nd) { set_error("%s: axis %d of a %d-D face field", who, axis, l->nd); return false; }
+  return staggered_layout_ok(who, what, l, axis);
+}
+
 // one-pass kernels of the launch-bound levels (kernels_small.hip), tried by the entry points when the large-level kernels decline
 bool small_two_stage_ok(const examg_layout_t *lu, const examg_layout_t *lf, const examg_stencil_t *st, const Box &box);
 int launch_small_two_stage(bool col, int var, const examg_layout_t *lu, const double *u_in, double *u_out, const examg_layout_t *lf, const double *rhs,
@@ -477,17 +498,16 @@ static inline Geom make_geom(const examg_geom_t *g) {
   return Geom{g->pos_begin[0], g->pos_begin[1], g->pos_begin[2], g->h[0], g->h[1], g->h[2]};
 }
 // Evaluation point of iterator index (i0, i1, i2): the node position index * h + pos_begin, or the cell centre
-// (index * h + pos_begin) + 0.5 * h (grid/ir/IR_VF_CellCenter.scala:97-100).
-template <bool CELL>
+// (index * h + pos_begin) + 0.5 * h (grid/ir/IR_VF_CellCenter.scala:97-100).  LOC: 0 the node, 1 the cell centre, 2 + a the centre of the
+// face normal to axis a -- the node position on axis a, the cell centre on the other axes.
+template <int LOC>
 __host__ __device__ __forceinline__ void point_position(const Geom &g, int i0, int i1, int i2, double &x, double &y, double &z) {
   x = i0 * g.h0 + g.pb0;
   y = i1 * g.h1 + g.pb1;
   z = i2 * g.h2 + g.pb2;
-  if (CELL) {
-    x = x + 0.5 * g.h0;
-    y = y + 0.5 * g.h1;
-    z = z + 0.5 * g.h2;
-  }
+  if (LOC != 0 && LOC != 2) x = x + 0.5 * g.h0;
+  if (LOC != 0 && LOC != 3) y = y + 0.5 * g.h1;
+  if (LOC != 0 && LOC != 4) z = z + 0.5 * g.h2;
 }
 
 // A point function: a postfix program (include/examg.h), evaluated in the order of the expression tree.  W: the program may read the
@@ -545,13 +565,13 @@ static inline GridGeom make_geom(const examg_grid_t *g) { return GridGeom{g->nod
 
 // The value of a point function at iterator index (i0, i1, i2): the ONE place where the point-expression kernels (kernels_blas.hip)
 // turn an index into a position -- the uniform formula, or the tables (position x[i], width x[i + 1] - x[i]; 0.0 on an axis without table)
-template <bool CELL, class F>
+template <int CELL, class F>
 __device__ __forceinline__ double eval_point(const Geom &g, const F &fn, int i0, int i1, int i2) {
   double px, py, pz;
   point_position<CELL>(g, i0, i1, i2, px, py, pz);
   return fn(px, py, pz);
 }
-template <bool CELL, class F>
+template <int CELL, class F>
 __device__ __forceinline__ double eval_point(const GridGeom &g, const F &fn, int i0, int i1, int i2) {
   double p[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
   if (g.n0) { p[0] = g.n0[i0 + g.ghost]; w[0] = g.n0[i0 + g.ghost + 1] - p[0]; }

@@ -193,7 +193,7 @@ k_dot_rows(LayoutDev lx, const double *__restrict__ x, LayoutDev ly, const doubl
 }
 
 
-template <class F, bool CELL = false, class G = Geom>
+template <class F, int CELL = 0, class G = Geom>
 __global__ void __launch_bounds__(RED_BLOCK)
 k_maxerr_partial(LayoutDev l, const double *__restrict__ x, G g, F fn, Box box, double *part) {
   const long long total = box.count();
@@ -216,7 +216,7 @@ __global__ void __launch_bounds__(RED_BLOCK) k_reduce_final(const double *part, 
 }
 
 // ---- analytic fills ---------------------------------------------------------------------------
-template <class F, bool CELL = false, class G = Geom>
+template <class F, int CELL = 0, class G = Geom>
 __global__ void __launch_bounds__(256) k_fill_fn(LayoutDev l, double *x, G g, F fn, Box box) {
   const long long total = box.count();
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
@@ -518,7 +518,7 @@ static inline GridGeom make_geom_for(const examg_grid_t *g, const examg_layout_t
 }
 static inline Geom make_geom_for(const examg_geom_t *g, const examg_layout_t *) { return make_geom(g); }
 
-template <class F, bool CELL = false, class GP = examg_geom_t>
+template <class F, int CELL = 0, class GP = examg_geom_t>
 static int max_err_impl(const char *who, const examg_layout_t *l_, const double *x, const GP *g, const F &fn,
                         const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream) {
   if (!l_ || !x || !g || !begin || !end || !result || !work) { set_error("examg_max_err: null argument"); return 1; }
@@ -535,7 +535,7 @@ static int max_err_impl(const char *who, const examg_layout_t *l_, const double 
   return 0;
 }
 
-template <class F, bool CELL = false, class GP = examg_geom_t>
+template <class F, int CELL = 0, class GP = examg_geom_t>
 static int fill_impl(const char *who, const examg_layout_t *l_, double *x, const GP *g, const F &fn, const int32_t *begin,
                      const int32_t *end, examg_stream_t stream) {
   if (!l_ || !x || !g || !begin || !end) { set_error("examg_fill: null argument"); return 1; }
@@ -651,13 +651,31 @@ extern "C" int examg_fill_expr(const examg_layout_t *l_, double *x, const examg_
 extern "C" int examg_max_err_expr_cell(const examg_layout_t *l_, const double *x, const examg_geom_t *g, const examg_expr_t *e,
                                        const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream) {
   if (!expr_ok(e)) return 1;
-  return max_err_impl<ExprEval, true>("k_maxerr_expr_cell", l_, x, g, ExprEval{*e}, begin, end, result, work, stream);
+  return max_err_impl<ExprEval, 1>("k_maxerr_expr_cell", l_, x, g, ExprEval{*e}, begin, end, result, work, stream);
 }
 
 extern "C" int examg_fill_expr_cell(const examg_layout_t *l_, double *x, const examg_geom_t *g, const examg_expr_t *e,
                                     const int32_t *begin, const int32_t *end, examg_stream_t stream) {
   if (!expr_ok(e)) return 1;
-  return fill_impl<ExprEval, true>("k_fill_expr_cell", l_, x, g, ExprEval{*e}, begin, end, stream);
+  return fill_impl<ExprEval, 1>("k_fill_expr_cell", l_, x, g, ExprEval{*e}, begin, end, stream);
+}
+
+extern "C" int examg_max_err_expr_face(int axis, const examg_layout_t *l_, const double *x, const examg_geom_t *g, const examg_expr_t *e,
+                                       const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream) {
+  if (!l_) { set_error("examg_max_err_expr_face: null argument"); return 1; }
+  if (!expr_ok(e) || !face_layout_ok("examg_max_err_expr_face", "field's", axis, l_)) return 1;
+  if (axis == 0) return max_err_impl<ExprEval, 2>("k_maxerr_expr_face", l_, x, g, ExprEval{*e}, begin, end, result, work, stream);
+  if (axis == 1) return max_err_impl<ExprEval, 3>("k_maxerr_expr_face", l_, x, g, ExprEval{*e}, begin, end, result, work, stream);
+  return max_err_impl<ExprEval, 4>("k_maxerr_expr_face", l_, x, g, ExprEval{*e}, begin, end, result, work, stream);
+}
+
+extern "C" int examg_fill_expr_face(int axis, const examg_layout_t *l_, double *x, const examg_geom_t *g, const examg_expr_t *e,
+                                    const int32_t *begin, const int32_t *end, examg_stream_t stream) {
+  if (!l_) { set_error("examg_fill_expr_face: null argument"); return 1; }
+  if (!expr_ok(e) || !face_layout_ok("examg_fill_expr_face", "field's", axis, l_)) return 1;
+  if (axis == 0) return fill_impl<ExprEval, 2>("k_fill_expr_face", l_, x, g, ExprEval{*e}, begin, end, stream);
+  if (axis == 1) return fill_impl<ExprEval, 3>("k_fill_expr_face", l_, x, g, ExprEval{*e}, begin, end, stream);
+  return fill_impl<ExprEval, 4>("k_fill_expr_face", l_, x, g, ExprEval{*e}, begin, end, stream);
 }
 
 extern "C" int examg_apply_dirichlet_expr(const examg_layout_t *l, double *x, const examg_geom_t *g, const examg_expr_t *e,

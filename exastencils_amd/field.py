@@ -242,6 +242,47 @@ class Colouring:
         return c
 
 
+@dataclass
+class MacSystem:
+    """The arrays and the operator of a staggered saddle-point system (include/examg.h, examg_mac_t): nd velocity components on the faces
+    of their axis, the pressure in the cells.  lu / u, lf / f, ld / dst: one FieldLayout / array per axis; lp / p, lfp / fp, ldp / dstp: the
+    pressure's.  A[d]: a constant star on u_d; the gradient at face i is bc[d] * p(i) + bm[d] * p(i - e_d), the divergence at cell i adds
+    cc[d] * u_d(i) + cp[d] * u_d(i + e_d).  Right-hand sides and destinations may be None where an entry point does not read them."""
+    nd: int
+    lu: list
+    u: list
+    lp: FieldLayout
+    p: object
+    A: list
+    bc: Sequence[float]
+    bm: Sequence[float]
+    cc: Sequence[float]
+    cp: Sequence[float]
+    lf: Optional[list] = None
+    f: Optional[list] = None
+    lfp: Optional[FieldLayout] = None
+    fp: object = None
+    ld: Optional[list] = None
+    dst: Optional[list] = None
+    ldp: Optional[FieldLayout] = None
+    dstp: object = None
+
+    def layouts(self):
+        """(name, layout) of every layout the system names."""
+        out = [("u_%d" % d, l) for d, l in enumerate(self.lu)] + [("pressure", self.lp)]
+        for names, ls, lp_ in (("rhs", self.lf, self.lfp), ("dst", self.ld, self.ldp)):
+            out += [("%s %d" % (names, d), l) for d, l in enumerate(ls or []) if l is not None]
+            if lp_ is not None:
+                out.append(("%s %d" % (names, self.nd), lp_))
+        return out
+
+    def check_elements(self, who: str):
+        """What the C struct cannot carry: complex and vector-valued fields are refused here, for every kernel layer alike."""
+        for name, l in self.layouts():
+            if getattr(l, "is_complex", False) or getattr(l, "is_vector", False):
+                raise ValueError("%s: the %s layout is %s; staggered systems take real scalar fields" % (who, name, "complex" if l.is_complex else "vector-valued"))
+
+
 def _axis(d: int, s: int) -> Tuple[int, int, int]:
     o = [0, 0, 0]
     o[d] = s

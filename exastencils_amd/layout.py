@@ -14,6 +14,9 @@ from typing import Sequence, Tuple
 from .lib import LayoutC
 
 
+FACE_LOCALIZATIONS = ("face_x", "face_y", "face_z")
+
+
 @dataclass(frozen=True)
 class FieldLayout:
     nd: int
@@ -28,8 +31,9 @@ class FieldLayout:
     # `[x, y, z] => [x / 2, y, z, x % 2]` (Testing/LayoutTrafo/rbgs.exa4:2).  Regions, iterator coordinates and boxes stay those of the
     # untransformed layout; only where a value lives changes.
     transform: int = 0
-    # "node" | "cell": Python-side only.  The C struct is the same for both (a cell layout is the one without duplicate layers);
-    # the localization travels as the choice of entry point (examg_*_cell).
+    # "node" | "cell" | "face_x" | "face_y" | "face_z": Python-side only.  The C struct is the same for all (a cell layout is the one without
+    # duplicate layers, a face layout has them on its own axis only); the localization travels as the choice of entry point (examg_*_cell,
+    # examg_*_face with the axis).
     localization: str = "node"
     # "real" | "complex": Python-side only, like the localization.  A point of a complex field is two consecutive doubles (re, im); every
     # count of the layout stays in POINTS and the element kind travels as the choice of entry point (examg_c*: include/examg.h).
@@ -62,6 +66,15 @@ class FieldLayout:
     @property
     def is_cell(self) -> bool:
         return self.localization == "cell"
+
+    @property
+    def is_face(self) -> bool:
+        return self.localization in FACE_LOCALIZATIONS
+
+    @property
+    def face_axis(self):
+        """The axis a face field's faces are normal to; None for node and cell layouts."""
+        return FACE_LOCALIZATIONS.index(self.localization) if self.is_face else None
 
     @property
     def is_complex(self) -> bool:
@@ -112,6 +125,36 @@ class FieldLayout:
             tot = pl[0] + g[0] + inner[0] + g[0]
             pr[0] = (align - tot % align) % align
         return FieldLayout(nd, inner, g, (0, 0, 0), tuple(pl), tuple(pr), True, communicates_ghost, localization="cell")
+
+    @staticmethod
+    def face(nd: int, ncells: Sequence[int], axis: int, ghost: int, communicates_dup: bool = True, communicates_ghost: bool = True,
+             align: int = 0) -> "FieldLayout":
+        """`Layout X< Real, Face_x >` (fieldlike/l4/L4_FieldLikeLayoutDecl.scala:53-57): on `axis` like a node field, one duplicate layer
+        per side and inner = cells - 1; on the other axes like a cell field, no duplicate layer and inner = cells.  Iterator coordinate 0
+        on the own axis is the lower boundary face; face i is the lower face of cell i; `loop over` covers [0, cells + 1) on the own
+        axis and [0, cells) on the others.  `align` pads x as FieldLayout.node / FieldLayout.cell do."""
+        if not 0 <= axis < nd:
+            raise ValueError("a %d-D field has no faces of axis %r" % (nd, axis))
+        if any(int(ncells[d]) < 1 for d in range(nd)):
+            raise ValueError("a Face field needs at least one cell per dimension")
+        du = tuple(1 if d == axis else 0 for d in range(3))
+        inner = tuple((int(ncells[d]) - du[d]) if d < nd else 1 for d in range(3))
+        g = tuple(ghost if d < nd else 0 for d in range(3))
+        pl, pr = [0, 0, 0], [0, 0, 0]
+        if align:
+            pl[0] = (align - g[0] % align) % align
+            tot = pl[0] + g[0] + du[0] + inner[0] + du[0] + g[0]
+            pr[0] = (align - tot % align) % align
+        return FieldLayout(nd, inner, g, du, tuple(pl), tuple(pr), communicates_dup, communicates_ghost, localization=FACE_LOCALIZATIONS[axis])
+
+    @property
+    def ncells(self) -> Tuple[int, ...]:
+        """Cells per axis of the block the field lives on."""
+        return tuple(self.inner[d] + self.dup[d] for d in range(self.nd))
+
+    def loop_box(self):
+        """The box of `loop over` the field: the duplicate and inner points, no ghost."""
+        return [0, 0, 0], [self.idx("DRE", d) if d < self.nd else 1 for d in range(3)]
 
     @staticmethod
     def node(nd: int, ncells: Sequence[int], ghost: int, communicates_dup: bool = True,

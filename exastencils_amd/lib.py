@@ -96,6 +96,13 @@ class BsysC(C.Structure):
                 ("dst", C.c_void_p * BSYS_MAX), ("A", C.POINTER(StencilC) * (BSYS_MAX * BSYS_MAX))]
 
 
+class MacC(C.Structure):
+    """examg_mac_t: the arrays and the operator of a staggered saddle-point system: nd face fields and the cell pressure (include/examg.h)."""
+    _fields_ = [("nd", C.c_int32), ("lu", LayoutC * 3), ("lp", LayoutC), ("lf", LayoutC * 3), ("lfp", LayoutC), ("ld", LayoutC * 3), ("ldp", LayoutC),
+                ("u", C.c_void_p * 3), ("p", C.c_void_p), ("f", C.c_void_p * 3), ("fp", C.c_void_p), ("dst", C.c_void_p * 3), ("dstp", C.c_void_p),
+                ("A", C.POINTER(StencilC) * 3), ("bc", C.c_double * 3), ("bm", C.c_double * 3), ("cc", C.c_double * 3), ("cp", C.c_double * 3)]
+
+
 MAX_EXPR = 256
 OPS = {"const": 0, "x": 1, "y": 2, "z": 3, "+": 4, "-": 5, "*": 6, "/": 7, "neg": 8, "sin": 9, "cos": 10, "exp": 11, "sinh": 12,
        "cosh": 13, "sqrt": 14, "pow": 15, "tan": 16, "log": 17, "fabs": 18, "max": 19, "min": 20, "tanh": 21}
@@ -216,6 +223,8 @@ SYMBOLS = [
     "examg_flux_step", "examg_flux_route", "examg_reduce_expr_cell",
     "examg_cstencil_op", "examg_cstencil_route", "examg_clincomb", "examg_cdot", "examg_crestrict", "examg_cprolong_add", "examg_cshift_div",
     "examg_cfrom_parts",
+    "examg_mac_op", "examg_mac_relax", "examg_mac_sweep", "examg_restrict_face", "examg_prolong_add_face", "examg_apply_bc_face",
+    "examg_fill_expr_face", "examg_max_err_expr_face",
 ]
 
 COMM_ID_BYTES = 128
@@ -381,6 +390,15 @@ def load(path=None):
     L.examg_cprolong_add.argtypes = [lp, vp, lp, vp, ip, ip, vp]
     L.examg_cshift_div.argtypes = [lp, vp, ip, dp, ip, ip, vp]
     L.examg_cfrom_parts.argtypes = [lp, vp, lp, vp, lp, vp, ip, ip, vp]
+    kp = C.POINTER(MacC)
+    L.examg_mac_op.argtypes = [C.c_int, kp, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp]
+    L.examg_mac_relax.argtypes = [kp, C.c_double, cp, ip, ip, vp]
+    L.examg_mac_sweep.argtypes = [kp, C.c_double, cp, ip, ip, vp]
+    L.examg_restrict_face.argtypes = [C.c_int, lp, vp, lp, vp, C.c_double, ip, ip, vp]
+    L.examg_prolong_add_face.argtypes = [C.c_int, lp, vp, lp, vp, ip, ip, vp]
+    L.examg_apply_bc_face.argtypes = [C.c_int, lp, vp, gp, C.c_int, ep, C.c_uint32, vp]
+    L.examg_fill_expr_face.argtypes = [C.c_int, lp, vp, gp, ep, ip, ip, vp]
+    L.examg_max_err_expr_face.argtypes = [C.c_int, lp, vp, gp, ep, ip, ip, vp, vp, vp]
     for name in SYMBOLS:
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         if name not in ("examg_version", "examg_last_error", "examg_device_count", "examg_reduce_work_bytes", "examg_exchange_workspace_bytes",

@@ -11,7 +11,7 @@ import ctypes as C
 from typing import Optional, Sequence
 
 from . import lib as _lib
-from .field import Colouring, MatrixStencil, Stencil, fn_expr  # noqa: F401  (Colouring: the value type of the coloured entry points)
+from .field import Colouring, MacSystem, MatrixStencil, Stencil, fn_expr  # noqa: F401  (Colouring: the value type of the coloured entry points)
 from .lib import NL_ADD, NL_APPLY, NL_RESIDUAL, ExamgError, check, ivec  # noqa: F401  (NL_*: the modes of nl_op)
 
 
@@ -447,6 +447,104 @@ class HipOps:
         """What bsys_op does with these arguments: -1 refused (the reason in examg_last_error), 0 empty box, lib.BSYS_GATHER."""
         y = self._bsys(lu, u, lf, f, A, ld, dst)
         return int(self.L.examg_bsys_route(int(mode), C.byref(y), int(row_mask), ivec(begin), ivec(end)))
+
+    # -- staggered grids: face fields, the three-field operator and the box smoother ---------------------------
+    def _mac(self, sys: MacSystem, who: str):
+        """examg_mac_t of a MacSystem; the stencil structs live as long as the returned struct (`keep`)."""
+        sys.check_elements(who)
+        y = _lib.MacC()
+        y.nd = sys.nd
+        m = min(max(sys.nd, 0), 3)      # an nd the library refuses still reaches it
+        y.keep = []
+
+        def put(dst, l):
+            if l is not None:
+                cs = l.c_struct()
+                C.memmove(C.byref(dst), C.byref(cs), C.sizeof(_lib.LayoutC))
+
+        put(y.lp, sys.lp)
+        put(y.lfp, sys.lfp)
+        put(y.ldp, sys.ldp)
+        y.p = self.ptr(sys.p) if sys.p is not None else None
+        y.fp = self.ptr(sys.fp) if sys.fp is not None else None
+        y.dstp = self.ptr(sys.dstp) if sys.dstp is not None else None
+        for d in range(min(m, len(sys.u))):
+            put(y.lu[d], sys.lu[d])
+            y.u[d] = self.ptr(sys.u[d]) if sys.u[d] is not None else None
+            if sys.f is not None and sys.f[d] is not None:
+                put(y.lf[d], sys.lf[d])
+                y.f[d] = self.ptr(sys.f[d])
+            if sys.dst is not None and sys.dst[d] is not None:
+                put(y.ld[d], sys.ld[d])
+                y.dst[d] = self.ptr(sys.dst[d])
+            y.bc[d], y.bm[d], y.cc[d], y.cp[d] = float(sys.bc[d]), float(sys.bm[d]), float(sys.cc[d]), float(sys.cp[d])
+            st = sys.A[d]
+            if st is None:
+                continue
+            sc = _lib.StencilC()
+            sc.nent = len(st.offsets)
+            sc.diag = st.offsets.index((0, 0, 0)) if (0, 0, 0) in st.offsets else 0
+            for k, o in enumerate(st.offsets[:_lib.MAXE]):
+                for t in range(3):
+                    sc.off[k][t] = o[t]
+                sc.coef[k] = st.coefs[k] if st.coefs else 0.0
+            if st.cfield is not None:
+                sc.cfield = self.ptr(st.cfield)
+                sc.clayout = st.clayout.c_struct()
+            y.keep.append(sc)
+            y.A[d] = C.pointer(sc)
+        return y
+
+    @staticmethod
+    def _row_boxes(nd: int, begin, end):
+        """One box per row, flattened: begin[r] / end[r] are the (x, y, z) of row r; None for a row outside the mask."""
+        n = max(nd, 0) + 1
+        b, e = (C.c_int32 * (3 * 4))(), (C.c_int32 * (3 * 4))()
+        for r in range(min(n, 4)):
+            if r < len(begin) and begin[r] is not None:
+                for t in range(3):
+                    b[3 * r + t], e[3 * r + t] = int(begin[r][t]), int(end[r][t])
+        return b, e
+
+    def mac_op(self, mode: int, sys: MacSystem, row_mask: int, begin, end):
+        """dst_r = row r of the staggered operator (lib.SYS_APPLY) or f_r minus it (lib.SYS_RESIDUAL) for the rows of row_mask, each on its
+        own box begin[r] .. end[r], in one launch (examg_mac_op)."""
+        y = self._mac(sys, "examg_mac_op")
+        b, e = self._row_boxes(sys.nd, begin, end)
+        check(self.L.examg_mac_op(int(mode), C.byref(y), int(row_mask), b, e, self._stream()), "examg_mac_op")
+
+    def mac_relax(self, sys: MacSystem, relax: float, col: Colouring, begin, end):
+        """The box solves of the cells of one colour, in place on u and p (examg_mac_relax)."""
+        y, cc = self._mac(sys, "examg_mac_relax"), col.c_struct()
+        check(self.L.examg_mac_relax(C.byref(y), float(relax), C.byref(cc), ivec(begin), ivec(end), self._stream()), "examg_mac_relax")
+
+    def mac_sweep(self, sys: MacSystem, relax: float, col: Colouring, begin, end):
+        """All colours of the box smoother in the reference's order (examg_mac_sweep)."""
+        y, cc = self._mac(sys, "examg_mac_sweep"), col.c_struct()
+        check(self.L.examg_mac_sweep(C.byref(y), float(relax), C.byref(cc), ivec(begin), ivec(end), self._stream()), "examg_mac_sweep")
+
+    def restrict_face(self, axis: int, lfine, rf, lc, fc, scale: float, begin, end):
+        check(self.L.examg_restrict_face(int(axis), C.byref(lfine), self.ptr(rf), C.byref(lc), self.ptr(fc), float(scale), ivec(begin), ivec(end),
+                                         self._stream()), "examg_restrict_face")
+
+    def prolong_add_face(self, axis: int, lc, uc, lfine, uf, begin, end):
+        check(self.L.examg_prolong_add_face(int(axis), C.byref(lc), self.ptr(uc), C.byref(lfine), self.ptr(uf), ivec(begin), ivec(end), self._stream()),
+              "examg_prolong_add_face")
+
+    def apply_bc_face(self, axis: int, l, x, geom, kind: int, expr, face_mask: int):
+        """`apply bc` of a face field: the node rule on the walls normal to `axis`, the cell rule on the others (examg_apply_bc_face)."""
+        check(self.L.examg_apply_bc_face(int(axis), C.byref(l), self.ptr(x), C.byref(geom), int(kind), C.byref(expr) if expr is not None else None,
+                                         int(face_mask), self._stream()), "examg_apply_bc_face")
+
+    def fill_expr_face(self, axis: int, l, x, geom, expr, begin, end):
+        check(self.L.examg_fill_expr_face(int(axis), C.byref(l), self.ptr(x), C.byref(geom), C.byref(expr), ivec(begin), ivec(end), self._stream()),
+              "examg_fill_expr_face")
+
+    def max_err_expr_face(self, axis: int, l, x, geom, expr, begin, end, out=None):
+        out = self.new_scalar() if out is None else out
+        check(self.L.examg_max_err_expr_face(int(axis), C.byref(l), self.ptr(x), C.byref(geom), C.byref(expr), ivec(begin), ivec(end), self.ptr(out),
+                                             self.ptr(self._work), self._stream()), "examg_max_err_expr_face")
+        return out
 
     # -- semilinear operators A * u + c(q) . u -------------------------------------------------------
     def nl_op(self, mode: int, lu, u, lq, q, lf, rhs, ld, dst, st: Stencil, c, begin, end):

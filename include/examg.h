@@ -963,6 +963,132 @@ int examg_bsys_relax(const examg_bsys_t *sys, double relax, const examg_colourin
                      examg_stream_t stream);
 int examg_bsys_route(int mode, const examg_bsys_t *sys, uint32_t row_mask, const int32_t *begin, const int32_t *end);
 
+/* ---- Staggered grids: velocities on the faces, the pressure in the cells (Examples/Stokes/2D_FV_Stokes_fromL4.exa4) ---------------
+ * `Layout X< Real, Face_x >` (fieldlike/l4/L4_FieldLikeLayoutDecl.scala:53-57): a FACE LAYOUT of axis a is the layout struct with dup = 1
+ * and inner = cells - 1 on axis a (like a node field) and dup = 0, inner = cells on every other axis (like a cell field).  Iterator
+ * coordinate 0 on the own axis is the lower boundary face, `loop over` covers [0, cells + 1) there and [0, cells) on the other axes; face i
+ * is the lower face of cell i.  Position of a face: the node position i * h + pos_begin on the own axis, the cell centre
+ * (i * h + pos_begin) + 0.5 * h on the others.  As for cell layouts the localization is the choice of entry point; the face entry points
+ * take the axis and refuse a layout whose dup pattern is not that of the axis, and every layout under a layout transformation.
+ *
+ * examg_mac_t names the arrays and the operator of the saddle-point system of nd = 2 or 3 velocity components u_d and the pressure p:
+ *   u[d], lu[d]     the unknown on the faces of axis d, a face layout of axis d with ghost >= 1 on every axis
+ *   p, lp           the pressure, a cell layout with ghost >= 1 on every axis
+ *   f[d], lf[d], fp, lfp        the right-hand sides;   dst[d], ld[d], dstp, ldp    the destinations of examg_mac_op
+ *   A[d]            a constant stencil on u_d: the centre (required) and axis neighbours at distance 1, each at most once, in any order;
+ *                   the order is significant
+ *   bc[d], bm[d]    the gradient at face i of axis d:  (bc_d * p(i)) + (bm_d * p(i - e_d))         (`B1` of the reference programs)
+ *   cc[d], cp[d]    the divergence at cell i adds      (cc_d * u_d(i)), then (cp_d * u_d(i + e_d))   (`C1`)
+ * Every array in its own layout; all layouts of one dimensionality and of the same number of cells per axis.  Scalar factors (1/h^2, the
+ * widths of a uniform finite-volume grid) are the caller's to fold into the coefficients, as for examg_sys_t.  Entries behind nd are ignored.
+ *
+ * Arithmetic, fp64, no contraction.  conv(A_d, u_d)(i) = the entries folded left to right in declared order: c_0 * u_d(i + o_0), then
+ * + c_k * u_d(i + o_k).
+ *
+ * examg_mac_op: for every row r of row_mask (bit r; rows 0 .. nd - 1 the momentum rows, row nd the continuity row) and every point of the
+ * row's box -- begin / end hold one box per row, begin[3 * r .. 3 * r + 2], in the iterator coordinates of the row's field -- in ONE launch:
+ *   row d < nd:   Au_d = conv(A_d, u_d)(i) + ((bc_d * p(i)) + (bm_d * p(i - e_d)))
+ *   row nd:       Au_p = the terms (cc_0 * u_0(i)), (cp_0 * u_0(i + e_0)), (cc_1 * u_1(i)), (cp_1 * u_1(i + e_1)), .. added one after the other
+ *   EXAMG_SYS_APPLY: dst_r = Au_r;   EXAMG_SYS_RESIDUAL: dst_r = f_r - Au_r
+ * Rows outside the mask are neither evaluated nor written, and their f, dst and boxes are not looked at.  Writes the boxes of the dst
+ * of the mask and nothing else.  No dst may be an unknown, a right-hand side of the mask or another dst of the mask.
+ *
+ * examg_mac_relax: one colour of the box smoother, in place:
+ *     `color with { i0 % 3, i1 % 3, loop over p { solve locally relax w { u@[0,0] => .. u@[1,0] => .. v@[0,0] => .. v@[0,1] => .. p => .. } } }`
+ * (2D_FV_Stokes_fromL4.exa4:588-601; solver/ir/IR_LocalSolve.scala, IR_LocalDirectInvert.scala:78-139: the accesses to the box's own
+ * unknowns form the matrix, everything else goes to the right-hand side).  [begin,end) is a box of CELLS inside the block, [0, cells).
+ * The unknowns of cell i are, per axis d, l_d = u_d(i) and h_d = u_d(i + e_d), and p(i).  A face on the domain boundary -- index 0 or
+ * cells on its own axis -- is no valid computation point (boundary/ir/IR_IsOnBoundary.scala:54-97): it is HELD, its row is the identity
+ * with its old value, its column stays, and it is not written back.  With a the centre of A_d, q its +e_d entry, m its -e_d entry
+ * (0.0 where A_d has none), per axis d:
+ *   tl = (the entries of A_d other than the centre and +e_d, folded in declared order over u_d about face i) + (bm_d * p(i - e_d))
+ *   th = (the entries of A_d other than the centre and -e_d, folded in declared order over u_d about face i + e_d) + (bc_d * p(i + e_d))
+ *        (no such entry: the pressure term alone)
+ *   r0 = f_d(i) - tl,        a00 = a, a01 = q, c0 = bc_d;      l_d held: r0 = l_d, a00 = 1.0, a01 = 0.0, c0 = 0.0
+ *   r1 = f_d(i + e_d) - th,  a11 = a, a10 = m, c1 = bm_d;      h_d held: r1 = h_d, a11 = 1.0, a10 = 0.0, c1 = 0.0
+ *   det = a00 * a11 - a01 * a10                                 (Cramer on the 2 x 2 block, as examg_sys_relax n = 2)
+ *   y0 = (r0 * a11 - a01 * r1) / det;   y1 = (a00 * r1 - a10 * r0) / det           (the block's inverse on its right-hand side)
+ *   z0 = (c0 * a11 - a01 * c1) / det;   z1 = (a00 * c1 - a10 * c0) / det           (.. on its border column)
+ * then, the terms added one after the other over d = 0 .. nd - 1,
+ *   sy = (cc_0 * y0_0) + (cp_0 * y1_0) + (cc_1 * y0_1) + ..;    sz = (cc_0 * z0_0) + (cp_0 * z1_0) + (cc_1 * z0_1) + ..
+ *   p_new = (sy - f_p(i)) / sz                                  (the Schur complement of the pressure is -sz)
+ *   l_new = y0_d - z0_d * p_new;   h_new = y1_d - z1_d * p_new  (back-substitution)
+ *   x = x_old + relax * (x_new - x_old) for the 2 * nd + 1 unknowns, held faces left out;  relax == 1.0: x = x_new, no arithmetic
+ * As with examg_sys_relax these are not the generator's bits (it emits an inverse times a vector).
+ * Colourings: two cells conflict when the box of one reads or writes an unknown of the other's; for full stars that is every offset of
+ * 1-norm 1 or 2 (and (2, +-1), (+-2, +-2) on two axes, which the accepted form separates too).  Accepted: one expression per axis,
+ * (s_d + i_d) % m_d with every m_d >= 3, the expressions in any order -- `i0 % 3, i1 % 3 [, i2 % 3]`.  Everything else is refused before
+ * anything is launched, with the conflict named: the parity of all indices, (i0 + i1 [+ i2]) % 2, which the finite-difference programs
+ * of the reference use (2D_FD_Stokes_fromL4.exa4), gives cells i and i + (-1, 1) one colour, the first reads u_0(i + e_1) and the second
+ * writes it (so do i and i + (-1, -1), the nearest conflict and the one the message names) -- that generated loop depends on its execution order.  The kernel enumerates the colour's cells densely, consecutive lanes
+ * consecutive cells of the colour in x.
+ *
+ * examg_mac_sweep: all m_0 * m_1 * .. colours in the reference's order (L4_ColorLoops.toRepeatLoops: the first expression fastest),
+ * col->rem ignored; it issues the examg_mac_relax launches one after the other and is bit-identical to those calls.
+ *
+ * All three refuse, before anything is launched: nd outside 2 .. 3; a layout whose dup pattern is not that of its localization, of
+ * another dimensionality, under a layout transformation or of other cell counts than the pressure's; unknowns without a ghost layer on
+ * some axis; A_d a stencil field, with an entry off the axes, of reach 2, repeated, or without the centre; a box (with the reach of the
+ * row's reads) that leaves an allocation; a destination that is an input.  The smoother also refuses a zero determinant of a 2 x 2 block
+ * and a zero sz for any pattern of held faces the block has (all faces of a cell held: fewer than 2 cells on every axis), and a box that
+ * leaves the cells of the block.  An empty box is a no-op that returns 0.  No allocation, no host synchronisation; capturable. */
+typedef struct examg_mac {
+  int32_t nd;
+  examg_layout_t lu[3], lp, lf[3], lfp, ld[3], ldp;
+  double *u[3], *p;
+  const double *f[3], *fp;
+  double *dst[3], *dstp;
+  const examg_stencil_t *A[3];
+  double bc[3], bm[3], cc[3], cp[3];
+} examg_mac_t;
+int examg_mac_op(int mode, const examg_mac_t *sys, uint32_t row_mask, const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_mac_relax(const examg_mac_t *sys, double relax, const examg_colouring_t *col, const int32_t *begin, const int32_t *end,
+                    examg_stream_t stream);
+int examg_mac_sweep(const examg_mac_t *sys, double relax, const examg_colouring_t *col, const int32_t *begin, const int32_t *end,
+                    examg_stream_t stream);
+
+/* Transfers of a face field of `axis` (operator/l4/L4_DefaultRestriction.scala:63-82): the Kronecker product of the node-linear operator
+ * on the own axis and the cell-linear one on the others.
+ * examg_restrict_face: for every coarse face I of [begin,end)
+ *   fc(I) = sum of (scale * W) * rf(fine), W = the product of the per-axis weights (powers of two: exact in any order),
+ *           own axis: the fine faces 2I - 1, 2I, 2I + 1 with 1/4, 1/2, 1/4;   other axes: the children 2I, 2I + 1 with 1/2 each;
+ *           the terms added in the entry order of the composed stencil: the x offset outermost, then y, then z, each ascending.
+ * Footprint: the fine faces [2 * begin - 1, 2 * (end - 1) + 1] on the own axis and [2 * begin, 2 * end) on the others must lie in the
+ * fine allocation (restricting over interior faces only, [1, cells), reads no ghost).
+ * examg_prolong_add_face: 2^d R^T -- linear on the own axis, the parent's value on the others.  For every fine face i of [begin,end)
+ *   own index even:  uf(i) = uf(i) + uc(c),  c = i / 2 on the own axis
+ *   own index odd:   uf(i) = uf(i) + ((0.5 * uc(c with (i + 1) / 2)) + (0.5 * uc(c with (i - 1) / 2)))
+ *   on the other axes c = floor(i / 2), also for the negative indices of ghost cells.
+ * Footprint: the coarse points named must lie in the coarse allocation; the own-axis indices of the box must not be negative.
+ * Both: 2-D or 3-D face layouts of `axis`, both of one dimensionality; a box that leaves an allocation and two arguments that are one
+ * array are errors, and nothing is launched.  Only the box of the destination is written.  An empty box is a no-op that returns 0. */
+int examg_restrict_face(int axis, const examg_layout_t *lfine, const double *rf, const examg_layout_t *lcoarse, double *fc, double scale,
+                        const int32_t *begin, const int32_t *end, examg_stream_t stream);
+int examg_prolong_add_face(int axis, const examg_layout_t *lcoarse, const double *uc, const examg_layout_t *lfine, double *uf,
+                           const int32_t *begin, const int32_t *end, examg_stream_t stream);
+
+/* `apply bc` of a face field of `axis` (boundary/ir/IR_BoundaryCondition.scala:38-45, IR_ApplyBCFunction.scala:53-83), every wall of
+ * face_mask (bit 2*d + (side > 0)) in ONE launch:
+ *   walls normal to `axis`, the NODE rule: the boundary face (own index 0 / cells) = g(position of the face); EXAMG_BC_DIRICHLET only
+ *   the other walls, the CELL rule of examg_apply_bc_cell: the ghost beside every face of the boundary row,
+ *     EXAMG_BC_DIRICHLET: ghost = (2.0 * g(wall point)) - interior;    EXAMG_BC_NEUMANN: ghost = interior
+ * g is the program `expr` evaluated as boundary/ir/IR_HandleBoundaries.scala:53-70 says: on the own axis the node position, on the
+ * wall's normal the wall's coordinate (index 0 below, cells above), elsewhere the cell centre.
+ * Ranges: tangentially the cells [0, cells) and, on the own axis, the faces [0, cells + 1); edge and corner ghosts are not written (as
+ * for examg_apply_bc_cell).  The node rule comes first, as in the reference's order of the walls for the x faces: where the cell rule
+ * reads a boundary face of a normal wall of the mask, `interior` is the value the node rule gives it, g(position of the face).
+ * Refused: EXAMG_BC_NEUMANN with a wall normal to `axis` in the mask, EXAMG_BC_NEGATE, a cell-rule wall without a ghost layer, a layout
+ * that is no face layout of `axis`. */
+int examg_apply_bc_face(int axis, const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
+                        uint32_t face_mask, examg_stream_t stream);
+
+/* examg_fill_expr / examg_max_err_expr with the program evaluated at the positions of the faces of `axis`: the same kernels,
+ * instantiated for the third localization. */
+int examg_fill_expr_face(int axis, const examg_layout_t *l, double *x, const examg_geom_t *g, const examg_expr_t *e, const int32_t *begin,
+                         const int32_t *end, examg_stream_t stream);
+int examg_max_err_expr_face(int axis, const examg_layout_t *l, const double *x, const examg_geom_t *g, const examg_expr_t *e,
+                            const int32_t *begin, const int32_t *end, double *result, void *work, examg_stream_t stream);
+
 /* ---- Semilinear operators: N(q; u) = A * u + c(q) . u ---------------------------------------------------------------------
  * A a constant stencil (cfield NULL; any entry list, 2-D or 3-D), c a point expression over the value of a node field q AT THE POINT:
  * `Stencil gamSten { [0, 0] => gam * exp ( Solution<active>@current ) }`, `Laplace * Solution + gamSten * Solution`

@@ -852,6 +852,11 @@ extern "C" int examg_init_helmholtz27(const examg_layout_t *lc, double *cfield, 
   if (!lc || !cfield || !g || !begin || !end) { set_error("examg_init_helmholtz27: null argument"); return 1; }
   if (!expr_ok(a)) return 1;
   if (lc->nd != 3) { set_error("examg_init_helmholtz27: 3-D only"); return 1; }
+  // cubic elements only: the kernel takes its half steps and 1 / (h * h) from h[0]
+  if (g->h[1] != g->h[0] || g->h[2] != g->h[0]) {
+    set_error("examg_init_helmholtz27: unequal mesh widths h = (%.17g, %.17g, %.17g); the elements must be cubes", g->h[0], g->h[1], g->h[2]);
+    return 1;
+  }
   const Box box = make_box(begin, end);
   if (box.count() == 0) return 0;
   if (!box_inside(lc, box, 0)) { set_error("examg_init_helmholtz27: box leaves the allocation"); return 1; }

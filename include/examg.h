@@ -492,8 +492,9 @@ int examg_init_varcoeff7(const examg_layout_t *lc, double *cfield, const examg_g
 /* 27-entry stencil field of -div(a grad u) - k^2 u (BASELINE.json config 4): trilinear elements with element-wise
  * constant a = a(element centre) (expression program), lumped mass, scaled by 1/h^3; ksq = k^2.
  * Entry order: (0,0,0), then the other 26 offsets (dx,dy,dz) with dz slowest and dx fastest: (-1,-1,-1), (0,-1,-1), (1,-1,-1),
- * (-1,0,-1), ... (1,1,1).  With h = g->h[0] and a_e = a(x +- 0.5 * h, y +- 0.5 * h, z +- 0.5 * h) for the eight elements around the
- * node, entry (dx,dy,dz) = (S * kf) / (h * h), S = the sum of a_e over the elements that hold both nodes (those on the side of every
+ * (-1,0,-1), ... (1,1,1).  The elements are cubes: g->h[1] != g->h[0] or g->h[2] != g->h[0] is refused before anything is launched (the
+ * error text names the three widths).  With h that one width and a_e = a(x +- 0.5 * h, y +- 0.5 * h, z +- 0.5 * h) for the eight
+ * elements around the node (x, y, z the node position index * h + pos_begin; the half step is the product (+-0.5) * h), entry (dx,dy,dz) = (S * kf) / (h * h), S = the sum of a_e over the elements that hold both nodes (those on the side of every
  * non-zero offset component; added with the x side outermost and the z side innermost, the lower side first) and kf = 1.0 / 3.0
  * for the centre, 0.0 across an edge (one non-zero component), -1.0 / 12.0 across a face or body diagonal; the centre entry then has
  * ksq subtracted.  Planes layout of lc, the points of [begin,end) only.  The stencil-field mechanism is the reference's

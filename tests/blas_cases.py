@@ -419,12 +419,15 @@ def stack_depth(program):
     return deepest
 
 
-def positions(geom, b, e, cell=False):
-    """Per dimension the exact positions index * h + pos_begin (+ h / 2 for cell centres) of the indices [b, e), as Fractions."""
+def positions(geom, b, e, cell=False, loc=None):
+    """Per dimension the exact positions index * h + pos_begin (+ h / 2 for cell centres) of the indices [b, e), as Fractions.
+    loc ("node", "cell", "face_x", "face_y", "face_z") overrides `cell`: a face of axis a is a node on a and a cell centre elsewhere."""
+    loc = ("cell" if cell else "node") if loc is None else loc
+    own = {"node": (0, 1, 2), "cell": (), "face_x": (0,), "face_y": (1,), "face_z": (2,)}[loc]
     out = []
     for d in range(3):
         h, pb = Fraction(geom.h[d]), Fraction(geom.pos_begin[d])
-        out.append([i * h + pb + (h / 2 if cell else 0) for i in range(b[d], e[d])])
+        out.append([i * h + pb + (0 if d in own else h / 2) for i in range(b[d], e[d])])
     return out
 
 

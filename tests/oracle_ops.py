@@ -321,6 +321,8 @@ class OracleOps:
         self.L.orc_init_varcoeff7(_lp(lc), self.ptr(cf), _gp(geom), int(coef_fn), _p4(params), _iv(begin), _iv(end))
 
     def init_helmholtz27(self, lc, cf, geom, coef_fn, params, begin, end):
+        if not geom.h[0] == geom.h[1] == geom.h[2]:          # as examg_init_helmholtz27 refuses them
+            raise ValueError("init_helmholtz27: unequal mesh widths h = (%r, %r, %r); the elements must be cubes" % tuple(geom.h))
         self.L.orc_init_helmholtz27(_lp(lc), self.ptr(cf), _gp(geom), int(coef_fn), _p4(params), _iv(begin), _iv(end))
 
     def pack(self, l, x, buf, begin, end):

@@ -60,6 +60,96 @@ __global__ void __launch_bounds__(256) k_apply_bc_cell(LayoutDev l, double *x, G
   }
 }
 
+// Every face of the mask with a kind and a program of its own (examg_apply_bc_cell_faces; EXAMG_BC_VALUE_MINUS of examg_apply_bc_cell).
+// The programs travel packed, one copy per distinct program: six examg_expr_t would not fit the kernel arguments.
+constexpr int FACE_PROG_MAX = EXAMG_MAX_EXPR;      // instructions of the distinct programs of one call together
+struct FaceTable {
+  int kind[6];             // per entry of CellFaces
+  int ps[6], pn[6];        // the program of the face: first instruction, length
+  unsigned char op[FACE_PROG_MAX];
+  double c[FACE_PROG_MAX];
+};
+
+// expr_eval over a packed program; (x, y, z) the cell centre, (nx, ny, nz) the node of the cell's own index (EXAMG_OP_NODE_*): the same
+// operations in the same order
+__device__ __forceinline__ double face_expr_eval(const FaceTable &e, int b, int n, double x, double y, double z, double nx, double ny, double nz) {
+  double st[24];
+  int sp = 0;
+  for (int i = b; i < b + n; ++i) {
+    switch (e.op[i]) {
+      case EXAMG_OP_CONST: st[sp++] = e.c[i]; break;
+      case EXAMG_OP_X: st[sp++] = x; break;
+      case EXAMG_OP_Y: st[sp++] = y; break;
+      case EXAMG_OP_Z: st[sp++] = z; break;
+      case EXAMG_OP_NODE_X: st[sp++] = nx; break;
+      case EXAMG_OP_NODE_Y: st[sp++] = ny; break;
+      case EXAMG_OP_NODE_Z: st[sp++] = nz; break;
+      case EXAMG_OP_ADD: --sp; st[sp - 1] = st[sp - 1] + st[sp]; break;
+      case EXAMG_OP_SUB: --sp; st[sp - 1] = st[sp - 1] - st[sp]; break;
+      case EXAMG_OP_MUL: --sp; st[sp - 1] = st[sp - 1] * st[sp]; break;
+      case EXAMG_OP_DIV: --sp; st[sp - 1] = st[sp - 1] / st[sp]; break;
+      case EXAMG_OP_NEG: st[sp - 1] = -st[sp - 1]; break;
+      case EXAMG_OP_SIN: st[sp - 1] = sin(st[sp - 1]); break;
+      case EXAMG_OP_COS: st[sp - 1] = cos(st[sp - 1]); break;
+      case EXAMG_OP_EXP: st[sp - 1] = exp(st[sp - 1]); break;
+      case EXAMG_OP_SINH: st[sp - 1] = sinh(st[sp - 1]); break;
+      case EXAMG_OP_COSH: st[sp - 1] = cosh(st[sp - 1]); break;
+      case EXAMG_OP_SQRT: st[sp - 1] = sqrt(st[sp - 1]); break;
+      case EXAMG_OP_POW: --sp; st[sp - 1] = pow(st[sp - 1], st[sp]); break;
+      case EXAMG_OP_TAN: st[sp - 1] = tan(st[sp - 1]); break;
+      case EXAMG_OP_LOG: st[sp - 1] = log(st[sp - 1]); break;
+      case EXAMG_OP_FABS: st[sp - 1] = fabs(st[sp - 1]); break;
+      case EXAMG_OP_MAX: --sp; st[sp - 1] = fmax(st[sp - 1], st[sp]); break;
+      case EXAMG_OP_MIN: --sp; st[sp - 1] = fmin(st[sp - 1], st[sp]); break;
+      case EXAMG_OP_TANH: st[sp - 1] = tanh(st[sp - 1]); break;
+      default: st[sp++] = __builtin_nan(""); break;
+    }
+  }
+  return st[0];
+}
+
+// Thread t -> (face, boundary cell) as in k_apply_bc_cell; the kind is the face's.  The faces of a cell field never read one another's
+// ghosts (edge and corner ghosts are not written), so the launch equals the single-face launches in any order.
+__global__ void __launch_bounds__(256) k_apply_bc_cell_faces(LayoutDev l, double *x, Geom g, CellFaces fc, FaceTable ft, int3 inner) {
+  const long long total = fc.start[fc.n];
+  for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+    int f = 0;
+    while (f + 1 < fc.n && t >= fc.start[f + 1]) ++f;
+    const Box &bx = fc.box[f];
+    const long long r = t - fc.start[f];
+    const int n0 = bx.n0(), n1 = bx.n1();
+    int i[3];
+    i[0] = bx.b0 + (int)(r % n0);
+    i[1] = bx.b1 + (int)((r / n0) % n1);
+    i[2] = bx.b2 + (int)(r / ((long long)n0 * n1));
+    const int d = fc.dim[f], up = fc.up[f], kind = ft.kind[f];
+    int o[3] = {i[0], i[1], i[2]};
+    o[d] += up ? 1 : -1;
+    const double interior = x[lidx(l, i[0], i[1], i[2])];
+    double v;
+    if (kind == EXAMG_BC_NEUMANN) {
+      v = interior;
+    } else if (kind == EXAMG_BC_NEGATE) {
+      v = -interior;
+    } else if (kind == EXAMG_BC_VALUE_MINUS) {
+      // g at the ghost cell itself: its centre, and the node of its own index
+      double p[3], q[3];
+      point_position<1>(g, o[0], o[1], o[2], p[0], p[1], p[2]);
+      point_position<0>(g, o[0], o[1], o[2], q[0], q[1], q[2]);
+      v = face_expr_eval(ft, ft.ps[f], ft.pn[f], p[0], p[1], p[2], q[0], q[1], q[2]) - interior;
+    } else {
+      // face centre: cell centres tangentially, the node position of the face (index 0 / inner) in the normal dimension
+      double p[3];
+      point_position<1>(g, i[0], i[1], i[2], p[0], p[1], p[2]);
+      const double hh[3] = {g.h0, g.h1, g.h2}, pb[3] = {g.pb0, g.pb1, g.pb2};
+      const int nidx = up ? (d == 0 ? inner.x : (d == 1 ? inner.y : inner.z)) : 0;
+      p[d] = nidx * hh[d] + pb[d];
+      v = (2.0 * face_expr_eval(ft, ft.ps[f], ft.pn[f], p[0], p[1], p[2], 0.0, 0.0, 0.0)) - interior;
+    }
+    x[lidx(l, o[0], o[1], o[2])] = v;
+  }
+}
+
 // ---- restriction ----------------------------------------------------------------------------------------------------------
 // fc(I) = sum_{a, b, c in {0,1}} (scale * 0.5^d) * rf(2I + (a, b, c)), terms added in the entry order of the composed stencil
 // kron(kron(Rx, Ry), Rz) (L4_StencilOps.kron: left entries outer, right entries inner): x offset outermost, then y, then z.
@@ -182,14 +272,8 @@ extern "C" int examg_debug_cell_narrow(int on) {
 }
 #endif
 
-// ncomp > 1: every component of a vector-valued field (examg_vec_*), the component the y dimension of the grid
-static int apply_bc_cell_impl(const char *who, const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
-                              uint32_t face_mask, examg_stream_t stream, int ncomp) {
-  if (!l || !x || !g) { set_error("%s: null argument", who); return 1; }
-  if (kind != EXAMG_BC_DIRICHLET && kind != EXAMG_BC_NEUMANN && kind != EXAMG_BC_NEGATE) { set_error("%s: unknown kind %d", who, kind); return 1; }
-  if (kind == EXAMG_BC_DIRICHLET && !expr_ok(expr)) return 1;
-  if (!cell_layout_ok(who, l)) return 1;
-  CellFaces fc;
+// the boundary row of cells of every face of the mask, in the order dimension, side; false: error text set
+static bool cell_faces(const char *who, const examg_layout_t *l, uint32_t face_mask, CellFaces &fc, int (&face_of)[6]) {
   fc.n = 0;
   fc.start[0] = 0;
   for (int d = 0; d < l->nd; ++d)
@@ -197,7 +281,7 @@ static int apply_bc_cell_impl(const char *who, const examg_layout_t *l, double *
       if (!(face_mask & (1u << (2 * d + side)))) continue;
       if ((side ? l->ghost_r[d] : l->ghost_l[d]) < 1) {
         set_error("%s: face %d of dim %d has no ghost layer", who, side, d);
-        return 1;
+        return false;
       }
       int b[3] = {0, 0, 0}, e[3] = {1, 1, 1};
       for (int t = 0; t < l->nd; ++t) {
@@ -211,9 +295,23 @@ static int apply_bc_cell_impl(const char *who, const examg_layout_t *l, double *
       fc.box[fc.n] = bx;
       fc.dim[fc.n] = d;
       fc.up[fc.n] = side;
+      face_of[fc.n] = 2 * d + side;
       fc.start[fc.n + 1] = fc.start[fc.n] + bx.count();
       ++fc.n;
     }
+  return true;
+}
+
+// ncomp > 1: every component of a vector-valued field (examg_vec_*), the component the y dimension of the grid
+static int apply_bc_cell_impl(const char *who, const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
+                              uint32_t face_mask, examg_stream_t stream, int ncomp) {
+  if (!l || !x || !g) { set_error("%s: null argument", who); return 1; }
+  if (kind != EXAMG_BC_DIRICHLET && kind != EXAMG_BC_NEUMANN && kind != EXAMG_BC_NEGATE) { set_error("%s: unknown kind %d", who, kind); return 1; }
+  if (kind == EXAMG_BC_DIRICHLET && !expr_ok(expr)) return 1;
+  if (!cell_layout_ok(who, l)) return 1;
+  CellFaces fc;
+  int face_of[6];
+  if (!cell_faces(who, l, face_mask, fc, face_of)) return 1;
   if (fc.n == 0) return 0;
   examg_expr_t none;
   if (kind != EXAMG_BC_DIRICHLET) {
@@ -240,15 +338,87 @@ static int apply_bc_cell_impl(const char *who, const examg_layout_t *l, double *
   return 0;
 }
 
+// the program of a face: the stack discipline of expr_ok; the node-position opcodes are operands of EXAMG_BC_VALUE_MINUS only
+static bool face_expr_ok(int kind, const examg_expr_t *e) {
+  if (kind != EXAMG_BC_VALUE_MINUS) return expr_ok(e);
+  if (!e || e->n < 1 || e->n > EXAMG_MAX_EXPR) { set_error("examg expression: null or too long"); return false; }
+  examg_expr_t q = *e;
+  for (int i = 0; i < q.n; ++i)
+    if (q.op[i] >= EXAMG_OP_NODE_X && q.op[i] <= EXAMG_OP_NODE_Z) q.op[i] = EXAMG_OP_X;      // an operand like the position
+  return expr_ok(&q);
+}
+
+// faces[2 * d + side]: the kind and the program of every face of the mask
+static int apply_bc_cell_faces_impl(const char *who, const examg_layout_t *l, double *x, const examg_geom_t *g, const examg_bc_face_t *faces,
+                                    uint32_t face_mask, examg_stream_t stream) {
+  if (!l || !x || !g || !faces) { set_error("%s: null argument", who); return 1; }
+  if (l->nd < 1 || l->nd > 3) { set_error("%s: bad layout dimensionality %d", who, l->nd); return 1; }
+  for (int f = 0; f < 2 * l->nd; ++f) {
+    if (!(face_mask & (1u << f))) continue;
+    const int kind = faces[f].kind;
+    if (kind != EXAMG_BC_DIRICHLET && kind != EXAMG_BC_NEUMANN && kind != EXAMG_BC_NEGATE && kind != EXAMG_BC_VALUE_MINUS) {
+      set_error("%s: unknown kind %d", who, kind);
+      return 1;
+    }
+    if ((kind == EXAMG_BC_DIRICHLET || kind == EXAMG_BC_VALUE_MINUS) && !face_expr_ok(kind, faces[f].expr)) return 1;
+  }
+  if (!cell_layout_ok(who, l)) return 1;
+  CellFaces fc;
+  int face_of[6];
+  if (!cell_faces(who, l, face_mask, fc, face_of)) return 1;
+  if (fc.n == 0) return 0;
+  FaceTable ft;
+  int used = 0;
+  for (int k = 0; k < 6; ++k) ft.kind[k] = EXAMG_BC_NEUMANN, ft.ps[k] = 0, ft.pn[k] = 0;
+  for (int k = 0; k < fc.n; ++k) {
+    const examg_bc_face_t &fa = faces[face_of[k]];
+    ft.kind[k] = fa.kind;
+    if (fa.kind != EXAMG_BC_DIRICHLET && fa.kind != EXAMG_BC_VALUE_MINUS) continue;
+    int same = -1;      // faces that name one program share its copy
+    for (int j = 0; j < k && same < 0; ++j)
+      if (ft.pn[j] > 0 && faces[face_of[j]].expr == fa.expr) same = j;
+    if (same >= 0) { ft.ps[k] = ft.ps[same]; ft.pn[k] = ft.pn[same]; continue; }
+    if (used + fa.expr->n > FACE_PROG_MAX) {
+      set_error("%s: the programs of the faces have more than %d instructions together", who, FACE_PROG_MAX);
+      return 1;
+    }
+    ft.ps[k] = used;
+    ft.pn[k] = fa.expr->n;
+    for (int i = 0; i < fa.expr->n; ++i) {
+      ft.op[used + i] = (unsigned char)fa.expr->op[i];
+      ft.c[used + i] = fa.expr->c[i];
+    }
+    used += fa.expr->n;
+  }
+  for (int i = used; i < FACE_PROG_MAX; ++i) ft.op[i] = 0, ft.c[i] = 0.0;
+  const int3 inner = make_int3(l->inner[0], l->inner[1], l->inner[2]);
+  long long nb = (fc.start[fc.n] + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  hipLaunchKernelGGL(k_apply_bc_cell_faces, dim3((unsigned)nb), dim3(256), 0, (hipStream_t)stream, make_layout(l), x, make_geom(g), fc, ft, inner);
+  EXAMG_CHECK_LAUNCH("k_apply_bc_cell_faces");
+  return 0;
+}
+
 extern "C" int examg_apply_bc_cell(const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
                                    uint32_t face_mask, examg_stream_t stream) {
+  if (kind == EXAMG_BC_VALUE_MINUS) {      // the kind that evaluates at the ghost cell: the kernel of the faces call, one program for every face
+    examg_bc_face_t faces[6];
+    for (int f = 0; f < 6; ++f) faces[f].kind = kind, faces[f].expr = expr;
+    return apply_bc_cell_faces_impl("examg_apply_bc_cell", l, x, g, faces, face_mask, stream);
+  }
   return apply_bc_cell_impl("examg_apply_bc_cell", l, x, g, kind, expr, face_mask, stream, 1);
+}
+
+extern "C" int examg_apply_bc_cell_faces(const examg_layout_t *l, double *x, const examg_geom_t *g, const examg_bc_face_t *faces,
+                                         uint32_t face_mask, examg_stream_t stream) {
+  return apply_bc_cell_faces_impl("examg_apply_bc_cell_faces", l, x, g, faces, face_mask, stream);
 }
 
 extern "C" int examg_vec_apply_bc_cell(int n, const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, uint32_t face_mask,
                                        examg_stream_t stream) {
   if (!l) { set_error("examg_vec_apply_bc_cell: null argument"); return 1; }
   if (!vec_fields_ok("examg_vec_apply_bc_cell", n, l, nullptr)) return 1;
+  if (kind == EXAMG_BC_VALUE_MINUS) { set_error("examg_vec_apply_bc_cell: EXAMG_BC_VALUE_MINUS; vector-valued fields take EXAMG_BC_NEUMANN only"); return 1; }
   if (kind != EXAMG_BC_NEUMANN) { set_error("examg_vec_apply_bc_cell: kind %d; vector-valued fields take EXAMG_BC_NEUMANN only", kind); return 1; }
   return apply_bc_cell_impl("examg_vec_apply_bc_cell", l, x, g, kind, nullptr, face_mask, stream, n);
 }

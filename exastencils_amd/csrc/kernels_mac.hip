@@ -678,6 +678,7 @@ extern "C" int examg_apply_bc_face(int axis, const examg_layout_t *l, double *x,
                                    examg_stream_t stream) {
   const char *who = "examg_apply_bc_face";
   if (!l || !x || !g) { set_error("%s: null argument", who); return 1; }
+  if (kind == EXAMG_BC_VALUE_MINUS) { set_error("%s: EXAMG_BC_VALUE_MINUS; face fields take EXAMG_BC_DIRICHLET or EXAMG_BC_NEUMANN", who); return 1; }
   if (kind != EXAMG_BC_DIRICHLET && kind != EXAMG_BC_NEUMANN) { set_error("%s: kind %d; face fields take EXAMG_BC_DIRICHLET or EXAMG_BC_NEUMANN", who, kind); return 1; }
   if (kind == EXAMG_BC_DIRICHLET && !expr_ok(expr)) return 1;
   int n[3];

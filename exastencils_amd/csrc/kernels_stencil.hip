@@ -847,7 +847,12 @@ int launch_reduce_sum(const double *part, int n, double *result, hipStream_t s);
 size_t reduce_work_doubles();
 
 // ---- examg_stencil_op: which kernel takes a call (stencil_route), the launchers, the entry point that switches on the route ----
-enum StencilRoute { SR_SPLIT_HALF, SR_ROWMARCH, SR_ZMARCH, SR_FIELD7, SR_FIELD27_REC, SR_FIELD27_PLANES, SR_GENERIC };
+enum StencilRoute { SR_SPLIT_HALF, SR_ROWMARCH, SR_ZMARCH, SR_FIELD7, SR_FIELD27_REC, SR_FIELD27_PLANES, SR_GENERIC, SR_YMARCH };
+
+// kernels_star2d.hip: the y-marching 2-D 5-point star
+bool star2d_wanted(const examg_layout_t *lu, const examg_stencil_t *st, const Box &box);
+int launch_star2d(int mode, const LayoutDev &lu, const double *u, const LayoutDev &lf, const double *rhs, const LayoutDev &ld, double *dst,
+                  const examg_stencil_t *st, double w, int colour, const Box &box, hipStream_t s);
 
 // The kernel of one stencil loop whose arguments have passed the checks; aliased: u == dst.  Launches nothing, sets no error text.
 // Every condition, threshold and debug override of the dispatch is here, in the order the kernels are tried; the launchers hold geometry only.
@@ -872,6 +877,8 @@ static StencilRoute stencil_route(int mode, const examg_layout_t *lu_, const exa
     const bool rows = rowmarch_wanted(box, colour) && (g_rm_on == 1 || !even_strides(lu, lf_ ? make_layout(lf_) : lu, make_layout(ld_)));
     return rows ? SR_ROWMARCH : SR_ZMARCH;
   }
+  // the 2-D 5-point constant star in a canonical order, from a threshold number of points (kernels_star2d.hip)
+  if (lu_->nd == 2 && colour_ok && !passthru && star2d_wanted(lu_, st, box)) return SR_YMARCH;
   // the 7-entry stencil field in the reference's entry order (kernels_stencilfield.hip); transformed coefficient layouts, `omega / diag(A)`: generic kernel
   if (stencilfield7_enabled() && lu_->nd == 3 && st->cfield && star7_order(st) == 1 && st->diag == 0 && colour < 0 && box.n0() >= 64 &&
       st->ctransform == EXAMG_CLAYOUT_PLANES && st->wform == EXAMG_WEIGHT_INV_TIMES)
@@ -997,6 +1004,7 @@ int stencil_loop(int mode, const examg_layout_t *lu_, const double *u, const exa
     case SR_FIELD7: return launch_stencilfield7(mode, lu, u, lf, rhs, ld, dst, make_layout(&st->clayout), st->cfield, w, box, s);
     case SR_FIELD27_REC: return launch_sf27(true, mode, lu, u, lf, rhs, ld, dst, st, w, box, s);
     case SR_FIELD27_PLANES: return launch_sf27(false, mode, lu, u, lf, rhs, ld, dst, st, w, box, s);
+    case SR_YMARCH: return launch_star2d(mode, lu, u, lf, rhs, ld, dst, st, w, colour, box, s);
     case SR_GENERIC: break;
   }
   return launch_generic(mode, lu, u, lf, rhs, ld, dst, st, w, colour, box, passthru ? 1 : 0, s);

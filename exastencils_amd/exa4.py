@@ -164,6 +164,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
         self._complex_names = set() # fields declared on a Complex<Real> layout (exa4_complex.py)
         self._complex_scratch: Dict[int, Field] = {}     # per level: the real field a `C = <real point expression>` loop fills first
         self._bc_depth = 0          # inside a boundary function that `apply bc` runs
+        self._bc_taken = set()      # ghost loops of the function body being executed that the launch of an earlier one covered
+        self._node_ops = False      # _compile_point_expr: vf_nodePosition_* as EXAMG_OP_NODE_* (the value of a ghost loop)
         self._cell_names = set()    # fields declared on a cell layout: never taken by a one-pass peephole or cross-statement fusion
         self._vector_names = set()  # fields declared on a vector-valued cell layout (exa4_vector.py)
         self._has_vector = False    # ... or a stencil whose entries are matrices: only then is a statement asked whether it names one
@@ -573,6 +575,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
             if m:
                 if self.grid is not None and m.group(1).startswith("cellCent"):
                     raise Exa4Unsupported("%s on a non-uniform grid" % name)
+                if self._node_ops and m.group(1).startswith("nodePos"):
+                    return [("n" + m.group(2), None)]
                 return [(m.group(2), None)]
             if self.grid is not None and name == CELL_VOLUME:       # the product of the widths of the point's cell
                 prog = [("wx", None), ("wy", None), ("*", None)]
@@ -786,6 +790,8 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
             elif len(n) == 2 and n[0] == "applybc" and isinstance(n[1], tuple) and n[1][0] == "fld":
                 for (fname, _), f in self.fields.items():      # `apply bc` of a field with a boundary function runs that function
                     bf = getattr(f, "bc_function", None)
+                    if bf is None and getattr(f, "cell_bc", None) is not None and f.cell_bc[0] == "function":
+                        bf = f.cell_bc[1]      # ... of a cell field: its ghost loops may name globals in their values
                     if fname == n[1][1] and bf is not None and bf not in seen:
                         seen.add(bf)
                         for fn in self.functions[bf]:
@@ -831,7 +837,10 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
             if k == "loop":
                 if s[4] is not None:
                     return False
-            elif k in ("comm", "applybc", "advance"):
+            elif k == "applybc":
+                if not self._bc_function_host_free(s[1]):
+                    return False
+            elif k in ("comm", "advance"):
                 continue
             elif k == "repeat":
                 if s[1][0] != "num" or s[2] is not None or not self._host_free_body(s[3], lvl):
@@ -858,6 +867,16 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
                     return False
             else:
                 return False
+        return True
+
+    def _bc_function_host_free(self, target) -> bool:
+        """`apply bc` of a cell field with a boundary function runs that function: its statements (a timer around the ghost loops, a
+        print) count like those of a called function."""
+        for (fname, flvl), f in self.fields.items():
+            bc = getattr(f, "cell_bc", None)
+            if fname == target[1] and bc is not None and bc[0] == "function":
+                if not all(self._host_free_body(fn.body, flvl) for fn in self.functions[bc[1]]):
+                    return False
         return True
 
     def _host_state(self):
@@ -1311,9 +1330,12 @@ class Exa4Program(LazyFusions, Peepholes, Builtins, Statements, Systems, BlockSy
         f, _ = self._field(target, fr)
         if self._has_vector and (f.layout.is_vector or self._touches_vector(("block", list(body)))):
             return self._exec_vector_loop(s, f, fr)      # (exa4_vector.py)
+        if id(s) in self._bc_taken:                       # a ghost loop that went into the launch of the one before it
+            self._bc_taken.discard(id(s))
+            return
         ghost = self._recognise_ghost_loop(s, f, fr)      # a boundary function's loop over one face (exa4_conservation.py)
         if ghost is not None:
-            return self._launch(ghost, None, None, None)
+            return self._launch_bc_faces(self._merge_bc_faces(ghost, fr))
         if f.layout.is_complex and only is not None:
             return self._exec_complex_only_loop(s, f, fr)
         if only is not None and not f.layout.is_cell and any(n and n[0] == "off" and n[1][0] == "fld" for n in _walk(("block", list(body)))):

@@ -5,10 +5,10 @@ examg_apply_bc_cell).  Reference: Examples/SWE/2D_FV_SWE.exa4; baseExt/l4/L4_Exp
 Everything here RECOGNISES: it hands back a LoopStmt record (exa4_statements.py) and launches nothing; the launcher issues the call."""
 from __future__ import annotations
 
-from .exa4_parser import Exa4Unsupported, _COORD, _GRIDW, _walk
+from .exa4_parser import Exa4Unsupported, _COORD, _GRIDW, _contains, _walk
 from .exa4_statements import LoopStmt
 from .flux import ZERO, FluxComp, FluxSpec, FluxTerm, field_program
-from .lib import (BC_NEGATE, BC_NEUMANN, FLUX_MAX_COMP, FLUX_MAX_ENTRIES, FLUX_MAX_FIELDS, FLUX_MAX_PROGS, FLUX_MAX_TERMS, MAX_NL_EXPR, NL_STACK,
+from .lib import (BC_NEGATE, BC_NEUMANN, BC_VALUE_MINUS, FLUX_MAX_COMP, FLUX_MAX_ENTRIES, FLUX_MAX_FIELDS, FLUX_MAX_PROGS, FLUX_MAX_TERMS, MAX_NL_EXPR, NL_STACK,
                   REDUCE_MAX, REDUCE_MIN)
 
 _EXPR = "__expr__"          # prefix of an `Expr` in the variables of a frame
@@ -286,8 +286,9 @@ class Conservation:
 
     # -- boundary functions ---------------------------------------------------------------------------------------------------------
     def _recognise_ghost_loop(self, s, f, fr):
-        """LoopStmt('bc_face') for `loop over F only ghost [d] on boundary { F = [-] F@[-d] }` on a cell field: the Neumann kind or the
-        reflecting wall of examg_apply_bc_cell on one face; None for every loop that is not a ghost loop of a cell field."""
+        """LoopStmt('bc_face') for `loop over F only ghost [d] on boundary { F = [-] F@[-d] }` or `{ F = E - F@[-d] }` on a cell field:
+        the Neumann kind, the reflecting wall or the value-minus-interior kind of examg_apply_bc_cell on one face (prog: kind, face bit,
+        program of E or None); None for every loop that is not a ghost loop of a cell field."""
         _, target, only, where, reduction, body = s
         if only is None or only[0] != "ghost" or not f.layout.is_cell:
             return None
@@ -296,20 +297,92 @@ class Conservation:
         nz = [t for t in range(3) if d[t] != 0]
         if not only[2] or len(nz) != 1 or nz[0] >= self.nd or abs(d[nz[0]]) != 1 or where is not None or reduction is not None:
             raise Exa4Unsupported("%s: ghost loops of cell fields are boundary functions -- one axis direction, `on boundary`, no condition" % what)
-        bad = Exa4Unsupported("%s: the body of a ghost loop must be `%s = %s@[..]` or `%s = -%s@[..]` with the cell inside the face" % ((what,) + (f.name,) * 4))
+        bad = Exa4Unsupported("%s: the body of a ghost loop must be `%s = %s@[..]`, `%s = -%s@[..]` or `%s = E - %s@[..]` (E a value or a point "
+                              "expression) with the cell inside the face" % ((what,) + (f.name,) * 6))
         stmts = self._expanded_body(body, fr)
         if len(stmts) != 1 or stmts[0][0] != "assign" or stmts[0][1] != "=" or stmts[0][2][0] != "fld":
             raise bad
         D, ds = self._field(stmts[0][2], fr)
-        rhs, kind = stmts[0][3], BC_NEUMANN
+        rhs, kind, E = stmts[0][3], BC_NEUMANN, None
         if rhs[0] == "neg":
             rhs, kind = rhs[1], BC_NEGATE
-        if rhs[0] != "off" or rhs[1][0] != "fld" or D is not f or self._field(rhs[1], fr) != (D, ds) or tuple(rhs[2]) != tuple(-x for x in d):
+        elif rhs[0] == "bin" and rhs[1] == "-" and rhs[3][0] == "off" and rhs[3][1][0] == "fld":
+            rhs, kind, E = rhs[3], BC_VALUE_MINUS, rhs[2]
+        if rhs[0] != "off" or rhs[1][0] != "fld" or D is not f or self._field(rhs[1], fr) != (D, ds):
             raise bad
+        if tuple(rhs[2]) + (0,) * (3 - len(rhs[2])) != tuple(-x for x in d):
+            if E is None:
+                raise bad
+            raise Exa4Unsupported("%s: `%s = E - %s@%s` reads a cell that is not the one inside the face (%s)"
+                                  % (what, f.name, f.name, list(rhs[2]), [-x for x in d[:len(rhs[2])]]))
+        prog = None
+        if E is not None:
+            if _contains(E, ("fld", "sten", "sentry")):
+                raise Exa4Unsupported("%s: a field access inside the value E of `%s = E - %s@[..]`" % (what, f.name, f.name))
+            if _has_off(E) or _contains(E, ("vfo",)):
+                raise Exa4Unsupported("%s: the value E of `%s = E - %s@[..]` with an offset access" % (what, f.name, f.name))
+            prog = self._ghost_value_program(E, D.level, fr)
         face = 1 << (2 * nz[0] + (1 if d[nz[0]] > 0 else 0))
         if self.domain.neighbor(nz[0], d[nz[0]]) is not None:
             face = 0      # an interior face: `on boundary` leaves nothing to do
-        return LoopStmt("bc_face", D, ds, prog=(kind, face))
+        return LoopStmt("bc_face", D, ds, prog=(kind, face, prog))
+
+    def _ghost_value_program(self, E, lvl, fr):
+        """The program of the value of a ghost loop (EXAMG_BC_VALUE_MINUS): evaluated at the ghost cell itself -- vf_cellCenter_* its centre,
+        vf_nodePosition_* the node of its own index (EXAMG_OP_NODE_*); a value without a position is a one-instruction program."""
+        from .lib import ExprC
+
+        if not self._over_position(E):
+            return ExprC.from_program([("const", float(self._eval(E, fr)))])
+        for n in _walk(E):
+            if n and n[0] == "id" and isinstance(n[1], str) and n[1].startswith("vf_boundary"):
+                raise Exa4Unsupported("%s in the value of a ghost loop (the value is taken at the ghost cell, not on the face)" % n[1])
+        key = ("ghostexpr", repr(E), lvl)
+        if key not in self._fn_cache:
+            self._node_ops = True      # _compile_point_expr: vf_nodePosition_* as the node-position opcodes
+            try:
+                self._fn_cache[key] = ExprC.from_program(self._compile_point_expr(E, lvl))
+            except ValueError as ex:
+                raise Exa4Unsupported(str(ex))
+            finally:
+                self._node_ops = False
+        return self._fn_cache[key]
+
+    def _merge_bc_faces(self, first: LoopStmt, fr):
+        """The ghost loops that follow `first` in the function body being executed and go into its launch: consecutive bc_face statements
+        of one function body that write distinct faces of the same field and slot, with nothing but startTimer / stopTimer of one timer
+        between them.  Returns the records (first included); the loops taken are skipped when the body reaches them."""
+        group = [first]
+        if not self.fuse or not self._cont or not self._cont[-1][4]:
+            return group
+        body, i = self._cont[-1][0], self._cont[-1][1]
+        faces, timer, taken = first.prog[1], None, []
+        j = i + 1
+        while j < len(body):
+            st = body[j]
+            if st[0] == "callstmt" and st[1][0] == "call" and st[1][1] in ("startTimer", "stopTimer") and st[1][1] not in self.functions:
+                name = repr(st[1][3])
+                if timer is not None and name != timer:
+                    break
+                timer = name
+                j += 1
+                continue
+            if st[0] != "loop":
+                break
+            try:
+                g, _ = self._field(st[1], fr)
+                k = self._recognise_ghost_loop(st, g, fr)
+            except Exa4Unsupported:
+                break      # the body meets the statement itself and names the refusal
+            if k is None or k.D is not first.D or k.ds != first.ds or (k.prog[1] & faces):
+                break
+            faces |= k.prog[1]
+            group.append(k)
+            taken.append(id(st))
+            timer = None
+            j += 1
+        self._bc_taken = set(taken)
+        return group
 
 
 def _has_off(node) -> bool:

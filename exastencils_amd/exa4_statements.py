@@ -261,10 +261,7 @@ class Statements:
         if kind.startswith("v_"):             # (exa4_vector.py) a loop over vector-valued cell fields: one launch over all components
             return self._launch_vector(k, b, e, colour)
         if kind == "bc_face":                 # (exa4_conservation.py) one face of a boundary function; no face: the block has a neighbour there
-            if k.prog[1]:
-                self.launches += 1
-                ops.apply_bc_cell(D.lc, D.data(k.ds), self.domain.geom(D.level), k.prog[0], None, k.prog[1])
-            return None
+            return self._launch_bc_faces([k])
         if kind == "reduce_expr":             # the device scalar goes back to the reduction loop, which reads it
             self.launches += 1
             return ops.reduce_expr_cell(int(k.s), D.lc, [X.data(s) for X, s in k.prog[0]], k.prog[1], b, e)
@@ -342,6 +339,27 @@ class Statements:
             ops.nl_smooth(U.lc, u, D.lc, d, lf, f, k.A, k.prog[0], k.prog[1], k.s, -1 if colour is None else colour, b, e)
         else:
             raise AssertionError(kind)
+
+    def _launch_bc_faces(self, group):
+        """The faces of a boundary function that stand together (exa4_conservation.py: _merge_bc_faces) as ONE launch, each with its kind
+        and program (examg_apply_bc_cell_faces); a single face, or a kernel layer without the faces call: one examg_apply_bc_cell each."""
+        live = [k for k in group if k.prog[1]]
+        if not live:
+            return None
+        D, ds, ops = live[0].D, live[0].ds, self.ops
+        geom = self.domain.geom(D.level)
+        if len(live) == 1 or not hasattr(ops, "apply_bc_cell_faces"):
+            for k in live:
+                self.launches += 1
+                ops.apply_bc_cell(D.lc, D.data(ds), geom, k.prog[0], k.prog[2], k.prog[1])
+            return None
+        faces, mask = [None] * 6, 0
+        for k in live:
+            faces[k.prog[1].bit_length() - 1] = (k.prog[0], k.prog[2])
+            mask |= k.prog[1]
+        self.launches += 1
+        ops.apply_bc_cell_faces(D.lc, D.data(ds), geom, faces, mask)
+        return None
 
     def _launch_coloured(self, k: LoopStmt, b, e, col) -> bool:
         """The loop of `k` on the points of the colour `col` of a multi-colouring: the stencil loops have a coloured kernel

@@ -107,7 +107,8 @@ MAX_EXPR = 256
 OPS = {"const": 0, "x": 1, "y": 2, "z": 3, "+": 4, "-": 5, "*": 6, "/": 7, "neg": 8, "sin": 9, "cos": 10, "exp": 11, "sinh": 12,
        "cosh": 13, "sqrt": 14, "pow": 15, "tan": 16, "log": 17, "fabs": 18, "max": 19, "min": 20, "tanh": 21}
 # ... and the widths of the point's cell, which the _grid entry points know beside them (every other entry point refuses them)
-GRID_OPS = dict(OPS, wx=23, wy=24, wz=25)
+# ... and the node of the cell's own index, an operand of the EXAMG_BC_VALUE_MINUS kind of examg_apply_bc_cell alone
+GRID_OPS = dict(OPS, wx=23, wy=24, wz=25, nx=26, ny=27, nz=28)
 
 
 class ExprC(C.Structure):
@@ -126,6 +127,11 @@ class ExprC(C.Structure):
             e.c[i] = float(c) if c is not None else 0.0
         e.program = list(prog)
         return e
+
+
+class BcFaceC(C.Structure):
+    """examg_bc_face_t: the kind and the program of one face of examg_apply_bc_cell_faces."""
+    _fields_ = [("kind", C.c_int32), ("expr", C.POINTER(ExprC))]
 
 
 MAX_NL_EXPR = 32
@@ -210,7 +216,7 @@ SYMBOLS = [
     "examg_transform_stencilfield", "examg_transform_field", "examg_layout_size", "examg_comm_peer_release", "examg_residual_restrict_one_pass", "examg_residual_restrict_blocks", "examg_prolong_add_blocks",
     "examg_comm_create_peer", "examg_comm_peer_alloc", "examg_comm_peer_connect", "examg_comm_peer_slab_bytes",
     "examg_comm_peer_gather_bytes", "examg_comm_status",
-    "examg_sum", "examg_add_scalar", "examg_fill_expr_cell", "examg_max_err_expr_cell", "examg_apply_bc_cell", "examg_restrict_cell",
+    "examg_sum", "examg_add_scalar", "examg_fill_expr_cell", "examg_max_err_expr_cell", "examg_apply_bc_cell", "examg_apply_bc_cell_faces", "examg_restrict_cell",
     "examg_prolong_add_cell",
     "examg_stencil_op_coloured", "examg_mcgs_sweep", "examg_mcgs_one_pass_eligible",
     "examg_sys_op", "examg_sys_relax", "examg_pointwise_mul",
@@ -231,7 +237,7 @@ COMM_ID_BYTES = 128
 PEER_HANDLE_BYTES = 128
 EXCH_DUP, EXCH_GHOST, EXCH_ALL, EXCH_CONCURRENT_AXES = 1, 2, 3, 4
 PASS_TMP_PLANES_VALID = 8
-BC_DIRICHLET, BC_NEUMANN, BC_NEGATE = 0, 1, 2
+BC_DIRICHLET, BC_NEUMANN, BC_NEGATE, BC_VALUE_MINUS = 0, 1, 2, 4
 CG_ALPHA_FROM_NORM, CG_NO_BC, CG_ZERO_START = 1, 2, 4
 GS_REFUSED, GS_EMPTY, GS_ONE_WORKGROUP, GS_TILED, GS_PER_HYPERPLANE = -1, 0, 1, 2, 3      # examg_gs_route
 
@@ -343,6 +349,7 @@ def load(path=None):
     L.examg_fill_expr_cell.argtypes = [lp, vp, gp, ep, ip, ip, vp]
     L.examg_max_err_expr_cell.argtypes = [lp, vp, gp, ep, ip, ip, vp, vp, vp]
     L.examg_apply_bc_cell.argtypes = [lp, vp, gp, C.c_int, ep, C.c_uint32, vp]
+    L.examg_apply_bc_cell_faces.argtypes = [lp, vp, gp, C.POINTER(BcFaceC), C.c_uint32, vp]
     L.examg_restrict_cell.argtypes = [lp, vp, lp, vp, C.c_double, ip, ip, vp]
     L.examg_prolong_add_cell.argtypes = [lp, vp, lp, vp, ip, ip, vp]
     cp = C.POINTER(ColouringC)
@@ -407,6 +414,9 @@ def load(path=None):
     if hasattr(L, "examg_debug_force_generic"):      # debug build only
         L.examg_debug_force_generic.argtypes = [C.c_int]
         L.examg_debug_force_generic.restype = C.c_int
+    if hasattr(L, "examg_debug_star2d"):             # debug build only: the y-marching 2-D star off / by the rule / wherever possible, rows per chunk
+        L.examg_debug_star2d.argtypes = [C.c_int, C.c_int]
+        L.examg_debug_star2d.restype = C.c_int
     if hasattr(L, "examg_debug_cell_narrow"):        # debug build only: the 8-byte form of the cell transfer kernels
         L.examg_debug_cell_narrow.argtypes = [C.c_int]
         L.examg_debug_cell_narrow.restype = C.c_int

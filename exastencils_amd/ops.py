@@ -312,10 +312,24 @@ class HipOps:
         return out
 
     def apply_bc_cell(self, l, x, geom, kind: int, expr, face_mask: int):
-        """kind: lib.BC_DIRICHLET (expr: the boundary value at the face centres), lib.BC_NEUMANN (ghost = interior) or lib.BC_NEGATE
-        (ghost = -interior: a reflecting wall); expr may be None for the last two."""
+        """kind: lib.BC_DIRICHLET (expr: the boundary value at the face centres), lib.BC_NEUMANN (ghost = interior), lib.BC_NEGATE
+        (ghost = -interior: a reflecting wall) or lib.BC_VALUE_MINUS (ghost = expr(ghost cell) - interior); expr may be None for the
+        two kinds without a value."""
         check(self.L.examg_apply_bc_cell(C.byref(l), self.ptr(x), C.byref(geom), int(kind), C.byref(expr) if expr is not None else None,
                                          int(face_mask), self._stream()), "examg_apply_bc_cell")
+
+    def apply_bc_cell_faces(self, l, x, geom, faces, face_mask: int):
+        """Every face of the mask in one launch (examg_apply_bc_cell_faces).  faces[2 * d + side]: (kind, expr) of the face, None
+        for a face outside the mask; kind lib.BC_* -- lib.BC_VALUE_MINUS: ghost = expr(ghost cell) - interior."""
+        from .lib import BcFaceC, ExprC
+
+        tab = (BcFaceC * 6)()
+        for f in range(6):
+            kind, expr = faces[f] if f < len(faces) and faces[f] is not None else (0, None)
+            tab[f].kind = int(kind)
+            tab[f].expr = C.pointer(expr) if expr is not None else C.POINTER(ExprC)()
+        check(self.L.examg_apply_bc_cell_faces(C.byref(l), self.ptr(x), C.byref(geom), tab, int(face_mask), self._stream()),
+              "examg_apply_bc_cell_faces")
 
     def restrict_cell(self, lfine, rf, lc, fc, scale: float, begin, end):
         check(self.L.examg_restrict_cell(C.byref(lfine), self.ptr(rf), C.byref(lc), self.ptr(fc), float(scale), ivec(begin), ivec(end),

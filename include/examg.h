@@ -706,10 +706,37 @@ int examg_max_err_expr_cell(const examg_layout_t *l, const double *x, const exam
  * Edge and corner ghosts are NOT written: tangentially each face covers the inner cells only.  The reference handles the
  * faces one after the other over a range that includes them; a cell stencil with entries off the axes would see the
  * difference, which is why the interpreter refuses those (only axis entries read ghosts, and every axis ghost is written
- * here exactly as the reference writes it).  Needs ghost >= 1 in every dimension of the mask. */
-enum { EXAMG_BC_DIRICHLET = 0, EXAMG_BC_NEUMANN = 1, EXAMG_BC_NEGATE = 2 };
+ * here exactly as the reference writes it).  Needs ghost >= 1 in every dimension of the mask.
+ *
+ *   EXAMG_BC_VALUE_MINUS: ghost = g(ghost cell) - interior         (a ghost loop with a value:
+ *                                                                   `loop over F only ghost [0, 1] on boundary { F = E - F@[0, -1] }`)
+ * ONE subtraction: it is neither the Dirichlet kind (no factor 2.0, another evaluation point) nor, with g = 0, EXAMG_BC_NEGATE --
+ * 0.0 - (+0.0) is +0.0 where -(+0.0) is -0.0.  g is `expr` evaluated AT THE GHOST CELL ITSELF, the loop index of the reference's ghost
+ * loop (index -1 below the first cell, index inner above the last), not at the face centre: EXAMG_OP_X/Y/Z are the centre of the
+ * ghost cell, (i * h + pos_begin) + 0.5 * h (`vf_cellCenter_*`), and EXAMG_OP_NODE_X/Y/Z the node of the ghost cell's own index,
+ * i * h + pos_begin (`vf_nodePosition_*`: the inner term of the cell-centre formula, the value examg_fill_expr uses for a node).  The
+ * node-position opcodes are operands of this kind only: every other kind and every other entry point refuses them ("unknown opcode").
+ * Tangential range, unwritten edge and corner ghosts and the ghost >= 1 check as for the other kinds.
+ * examg_vec_apply_bc_cell and examg_apply_bc_face refuse this kind.
+ *
+ * examg_apply_bc_cell_faces: every face of the mask in ONE launch, each with a kind and a program of its own -- faces[2*d + (side > 0)]
+ * for every bit of the mask (the other entries are not read; expr is not read for Neumann and NEGATE).  The faces of a cell field never
+ * read one another's ghosts, so the result has the bits of one examg_apply_bc_cell call per face, in any order.  The refusals of
+ * examg_apply_bc_cell apply per face; the distinct programs of one call may have EXAMG_MAX_EXPR instructions together (faces that
+ * name the same examg_expr_t share it). */
+/* (3 is no kind: it stays refused as "unknown kind", as every number that is none of these) */
+enum { EXAMG_BC_DIRICHLET = 0, EXAMG_BC_NEUMANN = 1, EXAMG_BC_NEGATE = 2, EXAMG_BC_VALUE_MINUS = 4 };
+#define EXAMG_OP_NODE_X 26
+#define EXAMG_OP_NODE_Y 27
+#define EXAMG_OP_NODE_Z 28
+typedef struct {
+  int32_t kind;              /* EXAMG_BC_* */
+  const examg_expr_t *expr;  /* the face's program (Dirichlet, VALUE_MINUS) */
+} examg_bc_face_t;
 int examg_apply_bc_cell(const examg_layout_t *l, double *x, const examg_geom_t *g, int kind, const examg_expr_t *expr,
                         uint32_t face_mask, examg_stream_t stream);
+int examg_apply_bc_cell_faces(const examg_layout_t *l, double *x, const examg_geom_t *g, const examg_bc_face_t *faces, uint32_t face_mask,
+                              examg_stream_t stream);
 
 /* RHS@coarser = scale * R * Residual with R the linear cell restriction (operator/l4/L4_DefaultRestriction.scala:37-43,63-90):
  * kron over the dimensions of [2i -> 0.5, 2i+1 -> 0.5], the mean of the 2^d child cells, weight 0.5^d exactly.
